@@ -4,8 +4,13 @@ rasterizer, one view per step) on the synthetic S1M scene (1M Gaussians, 1600x10
 N GPUs data-parallel over views with an RCCL exchange of the Gaussian parameter gradients per step (the SH gradient as an
 all-gather of 12 B per Gaussian and view expanded locally, the other 44 B all-reduced; dp/reducer.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
-  roofline     -- achieved vs peak HBM bandwidth of the dominant kernel, timed with HIP events
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line on rank 0: metric, value (iters/s),
+unit, higher_is_better, dtype, ms_per_step (the wall time of one timed step) and the workload.
+--dump-outputs DIR  after the timed steps, what the last timed step handed its caller (image, radii, gradients) as DIR/<name>.npy
+--full              everything else, on top of the same line:
+  roofline     -- per-kernel durations (an instrumented pass of its own) and achieved vs peak HBM bandwidth of the dominant kernel
+  extra legs   -- full training iteration, clustered scene, posed views, kernel_size 0.1, multi-million Gaussians, the reference's
+                  own kernels on this GPU, the opacity-field query (each can be left out with its --no-* option)
   cpu_baseline -- the oracle (CPU restatement of the reference) on a bounded sample, rank 0, N=1 only
 """
 import argparse
@@ -72,6 +77,9 @@ def parse():
     ap.add_argument("--width", type=int, default=1600)
     ap.add_argument("--height", type=int, default=1063)
     ap.add_argument("--kernel-size", type=float, default=0.0)
+    ap.add_argument("--full", action="store_true", help="also the per-kernel / roofline pass, the extra legs and the CPU baselines (the --no-* options below apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (image, radii, gradients; fixed seeded samples) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-full-loop", action="store_true", help="skip the full training-iteration leg (losses + Adam)")
     ap.add_argument("--cpu-baseline-gaussians", type=int, default=1_000_000, help="Gaussians of the cpu_baseline sample (default: the whole workload)")
@@ -158,14 +166,17 @@ def main():
         reducer = GradientAllReducer(list(params.values()), sh_params=None if os.environ.get("GOF_DP_DENSE_SH") == "1" else [params["shs"]])
 
     ex_events = []                                # (start, end) torch events around the exchange of every timed step
+    last = {}                                     # the forward's outputs of the last timed step (--dump-outputs)
 
-    def step(timed=False):
+    def step(timed=False, keep=False):
         for p in params.values():
             p.grad = None
         means2D.grad = None
         color, radii = rast(means3D=params["means3D"], means2D=means2D, shs=params["shs"], opacities=params["opacities"],
                             scales=params["scales"], rotations=params["rotations"])
         color.backward(dL)
+        if keep:
+            last.update(color=color.detach(), radii=radii)
         if distributed:
             if timed:                                 # the exchange ends with work.wait() on the current stream: events on it bracket the exposed part
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -188,26 +199,30 @@ def main():
     # ---- the timed region: exactly `steps` steps, no instrumentation inside (the exchange events are two stream markers) ----
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(True)
+        step(True, keep=(i == args.steps - 1))
     fence()
     elapsed = time.perf_counter() - t0
     exchange_ms = (sum(a.elapsed_time(b) for a, b in ex_events) / len(ex_events)) if ex_events else None
-    # ---- per-kernel durations: a SEPARATE pass of instrumented steps (HIP events recorded by the library on its launch stream
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["color"], last["radii"], params, means2D)
+    last.clear()
+    # ---- per-kernel durations (--full): a SEPARATE pass of instrumented steps (HIP events recorded by the library on its launch stream
     # around every launch; each event pair drains the queue between two kernels, so this pass is ~2 % slower than the timed one) ----
     kernel_times = None
     prof_steps = max(4, min(16, args.steps))
-    if rank == 0:
-        B.profile_enable(True)
-    if distributed:
-        reducer.profile = True                    # stream events around every phase of the exchange, on every rank
-    for _ in range(prof_steps):
-        step()
-    fence()
-    if rank == 0:
-        kernel_times = B.profile_report()
-        B.profile_enable(False)
+    if args.full:
+        if rank == 0:
+            B.profile_enable(True)
+        if distributed:
+            reducer.profile = True                # stream events around every phase of the exchange, on every rank
+        for _ in range(prof_steps):
+            step()
+        fence()
+        if rank == 0:
+            kernel_times = B.profile_report()
+            B.profile_enable(False)
     exchange_phases = None
-    if distributed:
+    if distributed and args.full:
         reducer.profile = False
         mine = dict(reducer.breakdown(), rank=rank, buckets_in_place_and_packed=reducer.last_buckets)
         exchange_phases = [None] * world
@@ -227,8 +242,6 @@ def main():
 
     out = None
     if rank == 0:
-        # ---- per-stage timing with HIP events on the launch stream + roofline of the dominant HBM kernel ----
-        stage = stage_times(B, sd, dL, dev, kernel_times, prof_steps)
         out = {
             "metric": "train iters/sec (fwd+bwd of the rasterizer, 1 view/GPU/step), S1M synthetic",
             "value": round(iters_per_s, 3), "unit": "iters/s", "n_gpus": (dist.get_world_size() if distributed else 1), "steps": args.steps, "warmup": args.warmup,
@@ -236,12 +249,18 @@ def main():
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": "S1M: %d Gaussians @ %dx%d, SH degree 3, kernel_size %.2f, fwd+bwd%s" % (
                 P, W, H, args.kernel_size, (" + RCCL gradient exchange (%s)" % reducer.last_exchange) if distributed else ""),
-                "num_rendered": stage["R"], "fwd_Msplats_per_s": round(P / (stage["fwd_ms"] * 1e-3) / 1e6, 2),
-                "fwd_ms": round(stage["fwd_ms"], 4), "bwd_ms": round(stage["bwd_ms"], 4),
-                "fwd_overlapped_second_stream_ms": round(stage["fwd_overlapped_ms"], 4),      # preprocess_fwd's stage 2, beside the binning chain (not in fwd_ms)
                 "parallelism": "dp%d (views)" % world},
-            "roofline": stage["roofline"],
         }
+        if args.full:
+            # ---- per-stage timing with HIP events on the launch stream + roofline of the dominant HBM kernel ----
+            stage = stage_times(B, sd, dL, dev, kernel_times, prof_steps)
+            cfg = out["config"]
+            out["config"] = {"workload": cfg["workload"],
+                             "num_rendered": stage["R"], "fwd_Msplats_per_s": round(P / (stage["fwd_ms"] * 1e-3) / 1e6, 2),
+                             "fwd_ms": round(stage["fwd_ms"], 4), "bwd_ms": round(stage["bwd_ms"], 4),
+                             "fwd_overlapped_second_stream_ms": round(stage["fwd_overlapped_ms"], 4),      # preprocess_fwd's stage 2, beside the binning chain (not in fwd_ms)
+                             "parallelism": cfg["parallelism"]}
+            out["roofline"] = stage["roofline"]
         if distributed:
             n = world
             kind = reducer.last_exchange
@@ -253,34 +272,68 @@ def main():
                                # pack + camera row (inside the backward), gather_wait / reduce_wait = EXPOSED part of the all-gather /
                                # all-reduce (compute stream waiting for the communication stream), expand = SH expansion kernel,
                                # bucket_pack / bucket_unpack = copies of gradients outside the rasterizer's allocation (none here)
-                               "per_rank_phases_ms": exchange_phases,
+                               "per_rank_phases_ms": exchange_phases,                  # (--full)
                                # optimistic pools on the data-parallel path (round 5): frames of rank 0 that had to be repeated because a
                                # pool sized from earlier frames was too small (forward again / blend stage again), and synchronising
                                # read-backs in front of a backward (the first frame of the shape only)
                                "pools_rank0": {k: B._stats[k] for k in ("mask_pool_redone_frames", "record_pool_redone_backwards", "backward_queries", "fused_redone_frames")},
                                "what": "exposed time of GradientAllReducer.all_reduce() per step (max over ranks), from stream events around it; "
                                        "the all-gather of the colour gradient starts inside the backward and overlaps preprocess_bwd"}
-        if world == 1 and not args.no_full_loop:
-            out["full_loop"] = full_loop(sd, dev, W, H)
-        if world == 1 and not args.no_clustered and P == 1_000_000:
-            out["clustered"] = clustered_leg(dev, P, W, H, focal, args.kernel_size, out["ms_per_step"])
-        if world == 1 and not args.no_views and P == 1_000_000:
-            out["views"] = views_leg(dev, sc, out["ms_per_step"])
-        if world == 1 and not args.no_kernel_size_leg and P == 1_000_000 and args.kernel_size == 0.0:
-            import synthetic_scenes as S_
-            out["kernel_size_0p1"] = scene_leg(dev, S_.scene_frustum(P, W=W, H=H, focal=focal, seed=0, kernel_size=0.1), "S1M, kernel_size 0.1", out["ms_per_step"], steps=20, warmup=3)
-        if world == 1 and not args.no_large_p:
-            out["large_p"] = large_p_leg(dev, out["ms_per_step"])
-        if world == 1 and not args.no_reference:
-            out["reference_same_gpu"] = reference_leg(sd, dL, out["ms_per_step"])
-        if world == 1 and not args.no_integrate:
-            out["integrate"] = integrate_leg(dev)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args, W, H, focal)
+        if args.full and world == 1:
+            run_extra_legs(out, args, sc, sd, dL, dev, P, W, H, focal)
         print(json.dumps(out))
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def run_extra_legs(out, args, sc, sd, dL, dev, P, W, H, focal):
+    """--full, one GPU: the legs beside the headline, each timed outside its timed region, keys added to `out`."""
+    if not args.no_full_loop:
+        out["full_loop"] = full_loop(sd, dev, W, H)
+    if not args.no_clustered and P == 1_000_000:
+        out["clustered"] = clustered_leg(dev, P, W, H, focal, args.kernel_size, out["ms_per_step"])
+    if not args.no_views and P == 1_000_000:
+        out["views"] = views_leg(dev, sc, out["ms_per_step"])
+    if not args.no_kernel_size_leg and P == 1_000_000 and args.kernel_size == 0.0:
+        import synthetic_scenes as S_
+        out["kernel_size_0p1"] = scene_leg(dev, S_.scene_frustum(P, W=W, H=H, focal=focal, seed=0, kernel_size=0.1), "S1M, kernel_size 0.1", out["ms_per_step"], steps=20, warmup=3)
+    if not args.no_large_p:
+        out["large_p"] = large_p_leg(dev, out["ms_per_step"])
+    if not args.no_reference:
+        out["reference_same_gpu"] = reference_leg(sd, dL, out["ms_per_step"])
+    if not args.no_integrate:
+        out["integrate"] = integrate_leg(dev)
+    if not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args, W, H, focal)
+
+
+# --dump-outputs: larger outputs are written as a fixed seeded sample of this many Gaussians / pixels (all of them below it): 26 MB at S1M
+DUMP_GAUSSIANS = 65536
+DUMP_PIXELS = 262144
+
+
+def _sample(n, k, seed):
+    """k sorted indices of range(n), the same for the same (n, k, seed); all of range(n) when n <= k"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(d, color, radii, params, means2D):
+    """What the timed path handed its caller in its last step: the forward's 9-channel image (colour, normal, depth, alpha,
+    distortion) and radii, and the backward's gradients of every input, as d/<name>.npy -- float32, radii as float64.  The image is
+    sampled by pixel (all channels of each), the per-Gaussian arrays by Gaussian (the same Gaussians in each)."""
+    os.makedirs(d, exist_ok=True)
+    C, H, W = color.shape
+    gi = torch.from_numpy(_sample(radii.shape[0], DUMP_GAUSSIANS, seed=11)).to(radii.device)
+    pi = torch.from_numpy(_sample(H * W, DUMP_PIXELS, seed=12)).to(color.device)
+    arrays = {"color": color.reshape(C, H * W)[:, pi].float(), "radii": radii[gi].double(), "grad_means2D": means2D.grad[gi]}
+    for k, p in params.items():
+        arrays["grad_" + k] = p.grad[gi]
+    for k, a in arrays.items():
+        a = a.detach().cpu().numpy()
+        np.save(os.path.join(d, k + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def stage_times(B, sd, dL, dev, kernel_times, steps):

@@ -32,6 +32,16 @@ LOCKSTEP_POINTS = [
     ("binning.hip", "            order[x * stride + s_off[x][bkt] + (r - lo)] = i;\n        }\n", "            order[x * stride + s_off[x][bkt] + (r - lo)] = i;\n        }\n        HIPEMU_WAVE_SYNC();\n"),
 ]
 
+# The developer-only statistics (-DGOF_STATS) sum a statement's count over the wave with a ballot before one atomic.  The statements sit
+# in divergent code (`if (has) STAT_ADD(5, 1)`), where the hardware pairs the ballot with the lanes of the exec mask and fibers cannot:
+# the emulated build adds per lane instead -- the same sums.  Same rules as LOCKSTEP_POINTS: every entry must match.
+STAT_POINTS = [
+    ("blend_forward.hip", "#define STAT_ADD(i, v) stat_add_wave(&g_fw_stats[i], (unsigned long long)(v), __builtin_constant_p(v) && (v) == 1)",
+     "#define STAT_ADD(i, v) atomicAdd(&g_fw_stats[i], (unsigned long long)(v))"),
+    ("integrate.hip", "#define ISTAT_ADD(i, v) istat_add_wave(&g_int_stats[i], (unsigned long long)(v), __builtin_constant_p(v) && (v) == 1)",
+     "#define ISTAT_ADD(i, v) atomicAdd(&g_int_stats[i], (unsigned long long)(v))"),
+]
+
 
 def lib_path(tag=""):
     return os.path.join(OUT, "libgof_hip_emu%s.so" % (("_" + tag) if tag else ""))
@@ -71,10 +81,10 @@ def _build_locked(asan, force, extra_flags, tag, verbose):
         text = open(src).read()
         orig = text
         text = DYN_LDS.sub(r"\1* \2 = reinterpret_cast<\1*>(hipemu::dynamic_lds());", text)
-        for fname, old, new in LOCKSTEP_POINTS:
+        for fname, old, new in LOCKSTEP_POINTS + STAT_POINTS:
             if fname == f:
                 if old not in text:
-                    raise RuntimeError("hipemu: lock-step point not found in %s: %r" % (f, old))
+                    raise RuntimeError("hipemu: rewrite point not found in %s: %r" % (f, old))
                 text = text.replace(old, new)
         if text != orig:
             text = '#line 1 "%s"\n' % src + text

@@ -112,3 +112,44 @@ def test_the_committed_pmc_pass_was_collected_on_the_current_blend_kernels():
         pytest.skip("no PMC pass of this round committed yet")
     pmc = json.load(open(f))
     assert b.pmc_pass_is_current(pmc, "blend_backward")        # the dominant kernel, whose traffic the bench line quotes (bench.py)
+
+
+def test_plain_run_is_lean_and_the_rest_is_behind_full(monkeypatch):
+    """`--full` (off by default) carries everything beyond the headline; `--dump-outputs DIR` is off by default."""
+    import sys
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_a_fixed_sample_under_64_mb(tmp_path):
+    """At the headline size every output is written as float32 / float64, 64 MB at most in all, and the sampled elements are the
+    same from run to run (the gradients here hold their own index, so the sample can be read back)."""
+    import types
+    import numpy as np
+    import torch
+    b = _bench_module()
+    P, H, W = 1_000_000, 1063, 1600
+    color = torch.arange(H * W, dtype=torch.float32).reshape(1, H, W).expand(9, H, W)
+    radii = torch.arange(P, dtype=torch.int32)
+    shapes = {"means3D": (3,), "shs": (16, 3), "opacities": (1,), "scales": (3,), "rotations": (4,)}
+    params = {k: types.SimpleNamespace(grad=torch.arange(P, dtype=torch.float32).reshape(P, *[1] * len(s)).expand(P, *s)) for k, s in shapes.items()}
+    means2D = types.SimpleNamespace(grad=torch.arange(P, dtype=torch.float32).reshape(P, 1).expand(P, 3))
+    runs = []
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), color, radii, params, means2D)
+        runs.append({f[:-4]: np.load(str(tmp_path / d / f)) for f in sorted(os.listdir(str(tmp_path / d)))})
+    a, c = runs
+    assert sorted(a) == sorted(["color", "radii", "grad_means2D"] + ["grad_" + k for k in shapes])
+    assert sum(x.nbytes for x in a.values()) <= 64 * 2 ** 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], c[k]), k
+    gi = a["radii"]
+    assert gi.shape == (b.DUMP_GAUSSIANS,) and np.all(np.diff(gi) > 0) and gi[-1] < P
+    for k, s in shapes.items():
+        assert a["grad_" + k].shape == (b.DUMP_GAUSSIANS,) + s and np.array_equal(a["grad_" + k].reshape(len(gi), -1)[:, 0], gi)
+    assert a["color"].shape == (9, b.DUMP_PIXELS) and np.all(np.diff(a["color"][0]) > 0)

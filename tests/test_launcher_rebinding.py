@@ -1,5 +1,6 @@
-"""CPU-only, needs /root/reference (skipped on the GPU box): launch/run_reference_script.py rebinds the RIGHT names of the
-unchanged reference -- every attribute it replaces exists in the reference with the same call signature."""
+"""CPU-only, needs the reference's Python scripts as __graft_entry__.build() stages them (oracle/_ref/refpy, byte-identical copies;
+skipped where they were not staged): launch/run_reference_script.py rebinds the RIGHT names of the unchanged reference -- every
+attribute it replaces exists in the reference with the same call signature."""
 import importlib.util
 import inspect
 import os
@@ -9,8 +10,8 @@ import types
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+REF = os.path.join(ROOT, "oracle", "_ref", "refpy")
+pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="oracle/_ref/refpy not staged (build() stages it where the reference exists)")
 
 
 def _load_launcher():
