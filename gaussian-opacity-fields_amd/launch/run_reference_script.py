@@ -29,7 +29,9 @@ What it does, in this order (nothing in the reference checkout is edited):
      imported module: for extract_mesh.py's `evaluage_alpha` (:17-34, the loop over all views per point set) the module body is
      executed without its `if __name__ == "__main__":` block, the name is pointed at mesh_extraction.evaluate_alpha (the same loop
      with the min / arg-min reduction over views fused into the point pass), then the block runs (run_script below;
-     GOF_TORCH_VIEW_REDUCE=1 keeps the script's own function).
+     GOF_TORCH_VIEW_REDUCE=1 keeps the script's own function).  extract_mesh_tsdf.py's `tsdf_fusion` (:16-83, Open3D's
+     VoxelBlockGrid on a CUDA device) is rebound the same way to tsdf_fusion.tsdf_fusion (the HIP TSDF fusion); its top-level
+     `import open3d` / `import open3d.core` resolve to shims/open3d when open3d is not installed.
 """
 import importlib
 import os
@@ -148,7 +150,7 @@ def main():
     ref_root = os.path.dirname(script)
     sys.path.insert(0, ref_root)
     sys.path.insert(0, PKG)
-    for mod in ("tetranerf.utils.extension",):
+    for mod in ("tetranerf.utils.extension", "open3d"):
         try:
             importlib.import_module(mod)
         except Exception:
@@ -189,6 +191,9 @@ def main():
         import mesh_extraction
         rebind["evaluage_alpha"] = lambda points, views, gaussians, pipeline, background, kernel_size, return_color=False: \
             mesh_extraction.evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color)
+    # extract_mesh_tsdf.py:16-83: the script's Open3D VoxelBlockGrid loop -> the HIP TSDF fusion (csrc/tsdf.hip)
+    import tsdf_fusion
+    rebind["tsdf_fusion"] = tsdf_fusion.tsdf_fusion
     run_script(script, rebind)
 
 
