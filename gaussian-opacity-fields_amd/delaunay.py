@@ -1,0 +1,83 @@
+"""Delaunay tetrahedralization on the GPU: the reference's ``tetranerf.utils.extension.cpp.triangulate`` (CGAL's
+Delaunay_triangulation_3, extract_mesh.py:51) without CGAL.
+
+    tets = triangulate(points)        # (N,3) float32 on a ROCm device -> (M,4) int32 on that device
+
+The kernels are ``gof_delaunay_*`` of libgof_hip.so (csrc/delaunay.hip, include/gof_delaunay_hip.h); the contract is DESIGN.md §3.7:
+exact predicates, ties broken by a symbolic perturbation, duplicates as one vertex (the lowest index), positively oriented cells in
+a canonical sorted order.  There is no host fallback: host tensors are refused.
+"""
+import ctypes as C
+
+import torch
+
+from diff_gaussian_rasterization import _backend as B
+
+__all__ = ["triangulate", "last_stats"]
+
+GOF_E_CAPACITY = -5
+_STAT_NAMES = ("rounds", "exact_evaluations", "peak_cells", "slow_insertions", "located_by_scan", "distinct_points", "capacity", "live_cells")
+
+lib = B.lib
+lib.gof_delaunay_ws_bytes.restype = C.c_size_t
+lib.gof_delaunay_ws_bytes.argtypes = [C.c_int64, C.c_int64]
+lib.gof_delaunay_build.restype = C.c_int
+lib.gof_delaunay_build.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]
+lib.gof_delaunay_emit.restype = C.c_int
+lib.gof_delaunay_emit.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+lib.gof_delaunay_stats.restype = C.c_int
+lib.gof_delaunay_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+
+# The initial arena: cells per point, learnt from the last call of at least 1024 points (its live cells, finite and infinite --
+# the arena holds both -- per point, with 10 % headroom), clamped to [6.5, 8] so that one unusual input neither starves nor inflates
+# the next calls; a call that needs more grows its own arena (GOF_E_CAPACITY) without changing this.
+_CPP_MIN, _CPP_MAX = 6.5, 8.0
+_cells_per_point = 7.0
+_last = {}
+
+
+def last_stats():
+    """Statistics of the last triangulate call: rounds, exact predicate evaluations, peak arena cells and bytes, ..."""
+    return dict(_last)
+
+
+def triangulate(points: torch.Tensor, capacity: int = None) -> torch.Tensor:
+    """Finite cells of the Delaunay tetrahedralization of `points` -> (M,4) int32 on points.device.
+
+    capacity: the initial cell arena (default: learnt, about 7 N + 64); the call doubles it and starts over while it is too small."""
+    global _cells_per_point
+    if points.dim() != 2 or points.size(1) != 3:
+        raise RuntimeError("triangulate: points must have dimensions (num_points, 3)")
+    if points.device.type != "cuda":
+        raise RuntimeError("triangulate (gfx950 backend) needs the points on a ROCm device, got %s" % points.device)
+    if points.dtype != torch.float32:
+        raise RuntimeError("triangulate: expected a float32 tensor, got %s" % points.dtype)
+    pts = points.contiguous()
+    n = int(pts.size(0))
+    if n >= 2 ** 31:
+        raise RuntimeError("triangulate: at most 2^31 - 1 points")
+    cap = int(capacity) if capacity else int(_cells_per_point * n) + 64
+    cap = max(16, min(cap, 2 ** 30 - 1))
+    with torch.cuda.device(pts.device):
+        while True:
+            nb = lib.gof_delaunay_ws_bytes(n, cap)
+            ws = torch.empty(nb, dtype=torch.uint8, device=pts.device)
+            m = C.c_int64()
+            rc = lib.gof_delaunay_build(n, pts.data_ptr(), cap, ws.data_ptr(), nb, C.byref(m), B._stream())
+            if rc == GOF_E_CAPACITY and m.value > cap:
+                del ws
+                cap = int(m.value)
+                continue
+            B._check(rc)
+            break
+        out = torch.empty((m.value, 4), dtype=torch.int32, device=pts.device)
+        B._check(lib.gof_delaunay_emit(ws.data_ptr(), m.value, out.data_ptr() if m.value else None, B._stream()))
+        st = (C.c_int64 * 8)()
+        B._check(lib.gof_delaunay_stats(ws.data_ptr(), st, B._stream()))
+    _last.clear()
+    _last.update(zip(_STAT_NAMES, list(st)))
+    _last["workspace_bytes"] = int(nb)
+    _last["cells"] = int(m.value)
+    if n >= 1024 and _last["live_cells"] > 0:
+        _cells_per_point = min(_CPP_MAX, max(_CPP_MIN, 1.1 * _last["live_cells"] / n))
+    return out
