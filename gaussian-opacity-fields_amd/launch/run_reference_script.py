@@ -32,6 +32,10 @@ What it does, in this order (nothing in the reference checkout is edited):
      GOF_TORCH_VIEW_REDUCE=1 keeps the script's own function).  extract_mesh_tsdf.py's `tsdf_fusion` (:16-83, Open3D's
      VoxelBlockGrid on a CUDA device) is rebound the same way to tsdf_fusion.tsdf_fusion (the HIP TSDF fusion); its top-level
      `import open3d` / `import open3d.core` resolve to shims/open3d when open3d is not installed.
+  7. evaluate_dtu_mesh.py:190-192 shells out to `python dtu_eval/eval.py ...` (Open3D, scikit-learn): the script's `os` becomes a
+     stand-in whose system() runs that one command in-process through mesh_eval's command line (the HIP Chamfer evaluation,
+     csrc/cloud.hip) and forwards everything else to the real os; GOF_DTU_EVAL_SUBPROCESS=1 leaves the script alone.  Given
+     dtu_eval/eval.py itself, the launcher runs mesh_eval's command line with the same arguments.
 """
 import importlib
 import os
@@ -142,11 +146,44 @@ def rebind_integrate_with_view_cache():
     GR.integrate = integrate
 
 
+class _OsWithInProcessEval:
+    """`os` for evaluate_dtu_mesh.py: system("python dtu_eval/eval.py <args>") runs mesh_eval.main(<args>) in this process, every
+    other attribute and command is the real os's."""
+
+    def __getattr__(self, name):
+        return getattr(os, name)
+
+    @staticmethod
+    def system(cmd):
+        import shlex
+        try:
+            words = shlex.split(cmd)
+        except ValueError:
+            return os.system(cmd)
+        if len(words) >= 2 and os.path.basename(words[0]).startswith("python") and words[1].replace("\\", "/").endswith("dtu_eval/eval.py"):
+            import mesh_eval
+            mesh_eval.main(words[2:])
+            return 0
+        return os.system(cmd)
+
+
+def dtu_eval_rebinding(script):
+    """the names to replace in `script`'s namespace for the DTU evaluation: {"os": stand-in} for evaluate_dtu_mesh.py"""
+    if os.path.basename(script) != "evaluate_dtu_mesh.py" or os.environ.get("GOF_DTU_EVAL_SUBPROCESS", "0") == "1":
+        return {}
+    return {"os": _OsWithInProcessEval()}
+
+
 def main():
     if len(sys.argv) < 2:
         print(__doc__)
         sys.exit(2)
     script = os.path.abspath(sys.argv[1])
+    if script.replace(os.sep, "/").endswith("dtu_eval/eval.py") and os.environ.get("GOF_DTU_EVAL_SUBPROCESS", "0") != "1":
+        sys.path.insert(0, PKG)
+        import mesh_eval
+        mesh_eval.main(sys.argv[2:])
+        return
     ref_root = os.path.dirname(script)
     sys.path.insert(0, ref_root)
     sys.path.insert(0, PKG)
@@ -194,6 +231,7 @@ def main():
     # extract_mesh_tsdf.py:16-83: the script's Open3D VoxelBlockGrid loop -> the HIP TSDF fusion (csrc/tsdf.hip)
     import tsdf_fusion
     rebind["tsdf_fusion"] = tsdf_fusion.tsdf_fusion
+    rebind.update(dtu_eval_rebinding(script))
     run_script(script, rebind)
 
 
@@ -219,6 +257,8 @@ def run_script(script, rebind):
         src = f.read()
     tree = ast.parse(src, filename=script)
     defined = {n.name for n in tree.body if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef))}
+    # (and the modules it imports under their own name at top level: evaluate_dtu_mesh.py's `import os`)
+    defined |= {a.asname or a.name for n in tree.body if isinstance(n, ast.Import) for a in n.names if "." not in (a.asname or a.name)}
     names = [k for k in rebind if k in defined]
     guards = [n for n in tree.body if _is_main_guard(n)]
     # only split when every guard block comes after everything else (otherwise the order of execution would change)
