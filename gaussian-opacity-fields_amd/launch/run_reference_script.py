@@ -36,6 +36,9 @@ What it does, in this order (nothing in the reference checkout is edited):
      stand-in whose system() runs that one command in-process through mesh_eval's command line (the HIP Chamfer evaluation,
      csrc/cloud.hip) and forwards everything else to the real os; GOF_DTU_EVAL_SUBPROCESS=1 leaves the script alone.  Given
      dtu_eval/eval.py itself, the launcher runs mesh_eval's command line with the same arguments.
+  8. given eval_tnt/run.py (Open3D 0.9: the last step of scripts/run_tnt.py), the launcher runs tnt_eval's command line (the HIP
+     Tanks-and-Temples F-score evaluation, csrc/cloud_reg.hip) with the same arguments; GOF_TNT_EVAL_SUBPROCESS=1 leaves the script
+     alone.
 """
 import importlib
 import os
@@ -174,11 +177,28 @@ def dtu_eval_rebinding(script):
     return {"os": _OsWithInProcessEval()}
 
 
+def _tnt_eval_main(argv):
+    import tnt_eval
+    return tnt_eval.main(argv)
+
+
+def tnt_eval_rebinding(script):
+    """what replaces `script` as a whole for the Tanks-and-Temples evaluation: {"main": tnt_eval's command line} for eval_tnt/run.py"""
+    if not os.path.abspath(script).replace(os.sep, "/").endswith("eval_tnt/run.py") or os.environ.get("GOF_TNT_EVAL_SUBPROCESS", "0") == "1":
+        return {}
+    return {"main": _tnt_eval_main}
+
+
 def main():
     if len(sys.argv) < 2:
         print(__doc__)
         sys.exit(2)
     script = os.path.abspath(sys.argv[1])
+    tnt = tnt_eval_rebinding(script)
+    if tnt:
+        sys.path.insert(0, PKG)
+        tnt["main"](sys.argv[2:])
+        return
     if script.replace(os.sep, "/").endswith("dtu_eval/eval.py") and os.environ.get("GOF_DTU_EVAL_SUBPROCESS", "0") != "1":
         sys.path.insert(0, PKG)
         import mesh_eval
