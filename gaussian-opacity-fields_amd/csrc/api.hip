@@ -65,7 +65,7 @@ __global__ void point_keys(int PN, const float4* pos, const uint32_t* offsets, c
                            uint32_t gx, uint32_t gy);
 __global__ void tile_ranges(uint32_t L, const uint32_t* tiles, uint2* ranges, int shift, const uint32_t* n_dev, const uint32_t* sort_error,
                             uint32_t* async_status);
-__global__ void rebuild_keys(uint32_t R, const uint32_t* tiles, const uint32_t* gids, const float* depths, uint64_t* keys);
+__global__ void rebuild_keys(uint32_t R, uint32_t P, const uint32_t* tiles, const uint32_t* gids, const float* depths, uint64_t* keys);
 
 __global__ void blend_forward(const uint2* ranges, const uint32_t* point_list, const SplatRec* rec, const float4* fconic, int W, int H,
                               float focal_x, float focal_y, const float* bg_color, float* final_T, uint32_t* n_contrib,
@@ -1328,7 +1328,7 @@ extern "C" int64_t gof_debug_fetch(const char* name, const GofRasterArgs* a, uin
     else if (n == "point_list" && binning_ws) { src = b.vals; count = R; bytes = (size_t)R * 4; }
     else if (n == "point_list_keys" && binning_ws && geom_ws) {
         if (dst_bytes < (size_t)R * 8) { set_error("dst too small"); return GOF_E_INVALID; }
-        if (R) hipLaunchKernelGGL(rebuild_keys, dim3((R + 255) / 256), dim3(256), 0, stream, R, b.tiles, b.vals, g.depths, static_cast<uint64_t*>(dst));
+        if (R) hipLaunchKernelGGL(rebuild_keys, dim3((R + 255) / 256), dim3(256), 0, stream, R, (uint32_t)a->P, b.tiles, b.vals, g.depths, static_cast<uint64_t*>(dst));
         if (hipGetLastError() != hipSuccess) { set_error("rebuild_keys launch failed"); return GOF_E_DEVICE; }
         return (int64_t)R;
     }

@@ -537,12 +537,14 @@ order_tiles(uint32_t ntiles, const uint2* __restrict__ ranges, const uint32_t* _
 
 // debug: the reference's 64-bit sort key of every sorted instance (tile << 32 | depth bits)
 __global__ void __launch_bounds__(256)
-rebuild_keys(uint32_t R, const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ gids, const float* __restrict__ depths,
+rebuild_keys(uint32_t R, uint32_t P, const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ gids, const float* __restrict__ depths,
              uint64_t* __restrict__ keys)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= R) return;
-    keys[i] = ((uint64_t)tiles[i] << 32) | (uint64_t)__float_as_uint(depths[gids[i]]);
+    // (R is the LAYOUT's size: behind the count of a sync-free frame the list holds whatever the workspace held -- no Gaussian's id)
+    const uint32_t id = gids[i];
+    keys[i] = ((uint64_t)tiles[i] << 32) | (uint64_t)(id < P ? __float_as_uint(depths[id]) : 0u);
 }
 
 } // namespace gof

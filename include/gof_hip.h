@@ -114,6 +114,12 @@ int gof_set_tight_tile_rects(int on);
 int gof_set_integrate_pixel_pass(int on);
 
 /* ---- workspace size queries (host only) ------------------------------------------------ */
+/* WORKSPACES MAY HOLD ANYTHING ON ENTRY UNLESS STATED.  No entry point reads a byte of a workspace that a call of the same frame has
+ * not written: a buffer fresh from an allocator that recycles memory (torch.empty: the previous frame's counters, queues and
+ * footprints) serves as well as a cleared one, and every result is bit-identical either way.  The same holds for outputs documented as
+ * fully written.  The exceptions are stated at the entry point: a workspace "filled by" an earlier call of the frame, and the outputs
+ * the caller pre-fills (gof_integrate_*: out_color zero, out_alpha_integrated 1, out_color_integrated 0; the running minima of
+ * gof_integrate_points_min).  tests/test_workspace_contents.py holds every entry point to this on poisoned buffers. */
 /* replaces required<GeometryState>(P)  (rasterizer_impl.cu:277, 188-204) */
 size_t gof_geom_bytes(int32_t P);
 /* ... for a forward / backward pair (gof_forward_prepare / _render / _fused, gof_backward*, gof_sh_grad_pack): the same layout without its
@@ -155,8 +161,9 @@ int gof_forward_prepare(const GofRasterArgs* args,
 /* The same stage in front of the opacity-field query (gof_integrate_view / gof_integrate_run; rasterizer_impl.cu:530-700 runs the same
  * preprocessCUDA there): same arguments, same outputs, and the per-Gaussian footprints COMPLETE -- besides the ray-space conic the forward
  * blend culls with, the conservative pixel box and the front depth the query's pixel and point passes prefilter with (ABI 12: since round 6
- * gof_forward_prepare / gof_forward_fused leave those two at "no statement", which costs a training forward ~40 % fewer fp64
- * instructions per Gaussian; a query run on a workspace of theirs is still exact, only slower). */
+ * gof_forward_prepare / gof_forward_fused leave those two at "no statement" -- into a gof_geom_bytes workspace they store the unbounded
+ * box, a gof_geom_bytes_forward one has no slot for it -- which costs a training forward ~40 % fewer fp64 instructions per Gaussian; a
+ * query run on a full-size workspace of theirs is still exact, only slower). */
 int gof_integrate_prepare(const GofRasterArgs* args,
                           void* geom_ws, size_t geom_bytes,
                           void* image_ws, size_t image_bytes,

@@ -45,6 +45,57 @@ def emu(monkeypatch):
     return lib
 
 
+# ---- what torch.empty returns (include/gof_hip.h: "workspaces may hold anything on entry unless stated") ---------------------------
+# The mirrors allocate every scratch buffer (SSIM and loss partials, the filter's and the densification's workspaces) and every output
+# with torch.empty / empty_like: on the device that is the caching allocator's recycled memory.  `poisoned` makes both return buffers
+# filled with 0xA5 or 0xFF (NaN floats, all-ones counters and cursors) for the duration of one test; under "stale" they are 0xA5 until
+# `.recycle()`, after which a request is served from the buffers handed out before -- same dtype, at least as many elements, the
+# smallest such first: what the caching allocator does -- as they were left, so a test runs a LARGER case first and its own case on
+# what that left behind.
+POISON = ["0xA5", "0xFF", "stale"]
+
+
+class poisoned:
+    def __init__(self, monkeypatch, fill):
+        assert fill in POISON, fill
+        self.byte = 0xFF if fill == "0xFF" else 0xA5
+        self.stale = fill == "stale"
+        self.out, self.free = [], []
+        real_empty, real_like = torch.empty, torch.empty_like
+
+        def fresh(t):
+            if t.numel() and t.is_contiguous():
+                t.reshape(-1).view(torch.uint8).fill_(self.byte)
+            elif t.numel():
+                t.fill_(float("nan") if t.is_floating_point() else (1 if t.dtype == torch.bool else -1))
+            return t
+
+        def empty(*size, **kw):
+            t = real_empty(*size, **kw)
+            if kw.get("out") is not None or t.layout != torch.strided or t.device.type != "cpu":
+                return t
+            fit = sorted((b for b in self.free if b.dtype == t.dtype and b.numel() >= t.numel()), key=lambda b: b.numel())
+            if fit and t.numel():
+                b = fit[0]
+                self.free = [x for x in self.free if x is not b]
+                return b.reshape(-1)[:t.numel()].view(t.shape)
+            if self.stale:
+                self.out.append(t)
+            return fresh(t)
+
+        def empty_like(t, **kw):
+            if kw.get("memory_format", torch.contiguous_format) not in (torch.contiguous_format,) and not t.is_contiguous():
+                return fresh(real_like(t, **kw))
+            kw.pop("memory_format", None)
+            return empty(t.shape, dtype=kw.pop("dtype", t.dtype), device=kw.pop("device", t.device), **kw)
+        monkeypatch.setattr(torch, "empty", empty)
+        monkeypatch.setattr(torch, "empty_like", empty_like)
+
+    def recycle(self):
+        """everything handed out so far is free again, holding what its user left in it"""
+        self.free, self.out = self.free + self.out, []
+
+
 def _close(a, b, tol, what):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     m = max(np.abs(b).max(), 1e-30)
@@ -53,6 +104,21 @@ def _close(a, b, tol, what):
 
 @pytest.mark.parametrize("shape", [(3, 101, 77), (3, 5, 300), (1, 1, 1), (2, 3, 40, 33)])
 def test_emulated_ssim_matches_oracle(emu, shape):
+    _ssim_matches_oracle(shape)
+
+
+@pytest.mark.parametrize("fill", POISON)
+@pytest.mark.parametrize("shape", [(3, 101, 77), (1, 1, 1), (2, 3, 40, 33)])
+def test_emulated_ssim_does_not_depend_on_what_its_buffers_held(emu, monkeypatch, shape, fill):
+    """the per-plane sums, the derivative maps and the scratch of gof_ssim from a poisoned torch.empty; "stale": after a larger image"""
+    pool = poisoned(monkeypatch, fill)
+    if fill == "stale":
+        _ssim_matches_oracle((4, 120, 90))
+        pool.recycle()
+    _ssim_matches_oracle(shape)
+
+
+def _ssim_matches_oracle(shape):
     import train_epilogue as T
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.rand(shape, generator=g)
@@ -104,6 +170,21 @@ def test_emulated_depth_to_normal_matches_oracle(emu, W, H):
 
 @pytest.mark.parametrize("shape", [(3, 37, 53), (1,), (8193,)])
 def test_emulated_l1_matches_oracle(emu, shape):
+    _l1_matches_oracle(shape)
+
+
+@pytest.mark.parametrize("fill", POISON)
+@pytest.mark.parametrize("shape", [(3, 37, 53), (1,), (8193,)])
+def test_emulated_l1_does_not_depend_on_what_its_buffers_held(emu, monkeypatch, shape, fill):
+    """the block partials of gof_l1 from a poisoned torch.empty; "stale": after a larger input"""
+    pool = poisoned(monkeypatch, fill)
+    if fill == "stale":
+        _l1_matches_oracle((20011,))
+        pool.recycle()
+    _l1_matches_oracle(shape)
+
+
+def _l1_matches_oracle(shape):
     from train_epilogue.loss_utils import _L1
     g = torch.Generator().manual_seed(5)
     a = torch.randn(shape, generator=g); b = torch.randn(shape, generator=g)
@@ -121,6 +202,21 @@ def test_emulated_l1_matches_oracle(emu, shape):
 def test_emulated_training_loss_matches_oracle(emu, W, H, lambdas):
     """the one-call loss (gof_train_loss: L1 + SSIM + depth -> normal consistency + distortion, train.py:150-186) and its gradient
     w.r.t. the rendering, against the oracle's composition of the reference's expressions under torch autograd"""
+    _training_loss_matches_oracle(W, H, lambdas)
+
+
+@pytest.mark.parametrize("fill", POISON)
+@pytest.mark.parametrize("W,H,lambdas", [(203, 131, (0.2, 0.05, 100.0)), (16, 16, (0.2, 0.0, 0.0)), (3, 3, (0.5, 1.0, 1.0))])
+def test_emulated_training_loss_does_not_depend_on_what_its_buffers_held(emu, monkeypatch, W, H, lambdas, fill):
+    """the six terms, the gradient image and the partials of gof_train_loss from a poisoned torch.empty; "stale": after a larger image"""
+    pool = poisoned(monkeypatch, fill)
+    if fill == "stale":
+        _training_loss_matches_oracle(230, 150, (0.2, 0.05, 100.0))
+        pool.recycle()
+    _training_loss_matches_oracle(W, H, lambdas)
+
+
+def _training_loss_matches_oracle(W, H, lambdas):
     import train_epilogue._backend as TB
     g = torch.Generator().manual_seed(W + H)
     rend = torch.rand((9, H, W), generator=g)
@@ -160,9 +256,23 @@ def _cloud(n, seed, kind="uniform"):
     return test_knn._cloud(n, seed, kind)
 
 
-@pytest.mark.parametrize("n,kind", [(1, "uniform"), (2, "uniform"), (3, "uniform"), (4, "uniform"), (255, "uniform"), (257, "uniform"),
-                                    (5000, "uniform"), (6000, "clustered"), (3000, "line"), (4000, "duplicates")])
+KNN_CASES = [(1, "uniform"), (2, "uniform"), (3, "uniform"), (4, "uniform"), (255, "uniform"), (257, "uniform"),
+             (5000, "uniform"), (6000, "clustered"), (3000, "line"), (4000, "duplicates")]
+
+
+@pytest.mark.parametrize("n,kind", KNN_CASES)
 def test_emulated_knn_matches_oracle(n, kind):
+    _knn_matches_oracle(n, kind, "zero")
+
+
+@pytest.mark.parametrize("n,kind", KNN_CASES)
+@pytest.mark.parametrize("fill", ["0xA5", "0xFF"])
+def test_emulated_knn_does_not_depend_on_what_its_workspace_held(n, kind, fill):
+    """include/gof_hip.h: workspaces may hold anything on entry (emu_binding.fill) -- the same comparison with the oracle"""
+    _knn_matches_oracle(n, kind, fill)
+
+
+def _knn_matches_oracle(n, kind, fill):
     lib = E.load()
     lib.gof_knn_ws_bytes.restype = C.c_size_t; lib.gof_knn_ws_bytes.argtypes = [C.c_int64]
     lib.gof_knn_mean_dist3.restype = C.c_int
@@ -170,7 +280,8 @@ def test_emulated_knn_matches_oracle(n, kind):
     pts = np.ascontiguousarray(_cloud(n, n), np.float32)
     out = np.zeros(n, np.float32)
     nb = lib.gof_knn_ws_bytes(n)
-    ws = E._aligned(nb)
+    with E.fill(fill):
+        ws = E._aligned(nb, what="knn ws")
     assert lib.gof_knn_mean_dist3(n, E._p(pts), E._p(out), E._p(ws), nb, None) == 0, lib.gof_last_error()
     want = KO.mean_dist3(pts)
     fin = np.isfinite(want)
@@ -200,6 +311,18 @@ def _mtets(lib, verts, tets, sdf, scales):
 
 @pytest.mark.parametrize("n", [(3, 3, 3), (14, 12, 10)])
 def test_emulated_marching_tets_match_oracle(n):
+    _marching_tets_match_oracle(n)
+
+
+@pytest.mark.parametrize("n", [(3, 3, 3), (14, 12, 10)])
+@pytest.mark.parametrize("fill", ["0xA5", "0xFF"])
+def test_emulated_marching_tets_do_not_depend_on_what_their_workspaces_held(n, fill):
+    """include/gof_hip.h: workspaces may hold anything on entry (emu_binding.fill) -- the same comparison with the oracle"""
+    with E.fill(fill):
+        _marching_tets_match_oracle(n)
+
+
+def _marching_tets_match_oracle(n):
     lib = E.load()
     verts, tets = S.freudenthal_tets(*n)
     rng = np.random.default_rng(7)
@@ -236,6 +359,21 @@ def emu_all(emu, monkeypatch):
 
 @pytest.mark.parametrize("P,ncam", [(1, 1), (1000, 3), (60_000, 12)])
 def test_emulated_compute_3d_filter_matches_oracle(emu_all, P, ncam):
+    _compute_3d_filter_matches_oracle(P, ncam)
+
+
+@pytest.mark.parametrize("fill", POISON)
+@pytest.mark.parametrize("P,ncam", [(1, 1), (1000, 3), (20_000, 5)])
+def test_emulated_compute_3d_filter_does_not_depend_on_what_its_buffers_held(emu_all, monkeypatch, P, ncam, fill):
+    """the output and the workspace of gof_compute_3d_filter from a poisoned torch.empty; "stale": after a larger cloud"""
+    pool = poisoned(monkeypatch, fill)
+    if fill == "stale":
+        _compute_3d_filter_matches_oracle(25_000, 6)
+        pool.recycle()
+    _compute_3d_filter_matches_oracle(P, ncam)
+
+
+def _compute_3d_filter_matches_oracle(P, ncam):
     import types
     import train_epilogue as T
     rng = np.random.default_rng(P + ncam)
@@ -306,6 +444,21 @@ def test_emulated_activations_match_oracle(emu_all):
 
 
 def test_emulated_densification_selection_and_row_surgery(emu_all, monkeypatch):
+    _densification_selection_and_row_surgery(emu_all, monkeypatch, 20_011)
+
+
+@pytest.mark.parametrize("fill", POISON)
+def test_emulated_densification_does_not_depend_on_what_its_buffers_held(emu_all, monkeypatch, fill):
+    """role, the three index lists, the compacted and gathered rows and the scan workspaces of gof_densify_select / gof_compact_rows /
+    gof_rows_gather from a poisoned torch.empty; "stale": after a larger model"""
+    pool = poisoned(monkeypatch, fill)
+    if fill == "stale":
+        _densification_selection_and_row_surgery(emu_all, monkeypatch, 26_003)
+        pool.recycle()
+    _densification_selection_and_row_surgery(emu_all, monkeypatch, 20_011)
+
+
+def _densification_selection_and_row_surgery(emu_all, monkeypatch, P):
     """gof_densify_select / gof_compact_rows / gof_rows_gather run from source against the reference's masks restated with torch on
     the host (scene/gaussian_model.py:631-707): grads = accum / denom with NaN -> 0; selected = norm(grads) >= max_grad or
     norm(grads_abs) >= Q; clone if max(scale) <= size_threshold, else split; the three ordered index lists; rows rebuilt by one
@@ -316,7 +469,6 @@ def test_emulated_densification_selection_and_row_surgery(emu_all, monkeypatch):
     for name in ("gof_densify_ws_bytes", "gof_densify_select", "gof_compact_rows", "gof_rows_gather"):
         getattr(emu_all, name).argtypes, getattr(emu_all, name).restype = getattr(real, name).argtypes, getattr(real, name).restype
     g = torch.Generator().manual_seed(9)
-    P = 20_011
     accum = torch.rand((P, 1), generator=g) * 3e-4
     accum_abs = torch.rand((P, 1), generator=g) * 6e-4
     denom = torch.randint(0, 5, (P, 1), generator=g).float()            # zeros: 0/0 = NaN -> 0

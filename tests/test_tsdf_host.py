@@ -60,6 +60,44 @@ def _p(a):
     return C.c_void_p(a.ctypes.data)
 
 
+# ---- what a buffer holds when the library receives it (include/gof_hip.h: "workspaces may hold anything on entry unless stated") ------
+# the product's TSDFVolume allocates the volume's arrays and both workspaces with torch.empty: recycled memory.  GOF_TSDF_FILL (read by
+# the child process) is "zero" (the default), "0xA5", "0xFF" (all-ones keys, counts and cursors, NaN voxels) or "stale": every buffer
+# holds what the buffer of the same role held when a LARGER volume (STALE_DONOR: more views, finer voxels, hence more blocks, a larger
+# table and larger frame sets) had been fused and extracted -- cut to the new size, or extended with 0xA5
+FILLS = ("zero", "0xA5", "0xFF", "stale")
+STALE_DONOR = ("boxes", 0.016)          # (scene, voxel size): finer than every EMU_SCENES entry
+_fill = "zero"
+_left = {}             # role -> the bytes the donor volume's last buffer of that role holds
+_recording = False
+
+
+def _buf(role, count, dtype):
+    """a workspace or volume array under the fill policy"""
+    a = np.empty(int(count), dtype)
+    raw = a.view(np.uint8)
+    if _fill == "zero":
+        raw[:] = 0
+    elif _fill == "0xFF":
+        raw[:] = 0xFF
+    else:
+        raw[:] = 0xA5
+        if _fill == "stale" and role in _left:
+            n = min(raw.size, _left[role].size)
+            raw[:n] = _left[role].view(np.uint8)[:n]
+    if _recording:
+        _left[role] = a          # (the live array: what it holds when the donor is done)
+    return a
+
+
+def _written(shape, dtype):
+    """an output the header documents as fully written: NaN / 0x7fffffff under a poison policy (zero as before otherwise)"""
+    a = np.zeros(shape, dtype)
+    if _fill != "zero":
+        a.fill(np.nan if a.dtype.kind == "f" else 0x7fffffff)
+    return a
+
+
 class EmuVolume:
     """TSDFVolume's host logic over numpy buffers and the emulated library (growth included: it starts at 4 blocks)"""
 
@@ -75,7 +113,8 @@ class EmuVolume:
 
     def _alloc(self, cap):
         tcap = 1 << (2 * cap - 1).bit_length()
-        keep = [np.empty(tcap, np.uint64), np.empty(tcap, np.uint32), np.empty(cap, np.uint64), np.empty(cap * 5 * 4096, np.float32), np.empty(4, np.uint32)]
+        keep = [_buf("table_keys", tcap, np.uint64), _buf("table_vals", tcap, np.uint32), _buf("block_keys", cap, np.uint64),
+                _buf("block_data", cap * 5 * 4096, np.float32), _buf("counter", 4, np.uint32)]
         vol = Vol(self.v, 8.0 * self.v, 16, 0, tcap, cap, *[a.ctypes.data for a in keep])
         self._check(self.lib.gof_tsdf_grow(C.byref(vol), C.byref(self.vol) if self.vol is not None else None, self.n, None))
         self.keep, self.vol = keep, vol
@@ -87,7 +126,7 @@ class EmuVolume:
         H, W = d.shape
         nf, nn = C.c_int64(), C.c_int64()
         while True:
-            ws = np.zeros(self.lib.gof_tsdf_frame_ws_bytes(self.S), np.uint8)
+            ws = _buf("frame ws", self.lib.gof_tsdf_frame_ws_bytes(self.S), np.uint8)
             rc = self.lib.gof_tsdf_touch(C.byref(self.vol), _p(d), H, W, _p(K32), _p(E32), 1.0, 6.0, _p(ws), ws.size, self.S, C.byref(nf), C.byref(nn), None)
             if rc != -5:
                 self._check(rc)
@@ -102,22 +141,23 @@ class EmuVolume:
 
     def blocks(self):
         """-> (coords [n,3] int32, data [n,5,16,16,16]) in storage order"""
-        co = np.zeros((self.n, 3), np.int32)
+        co = _written((self.n, 3), np.int32)
         self._check(self.lib.gof_tsdf_block_coords(C.byref(self.vol), self.n, _p(co), None))
         return co, self.keep[3][:self.n * 5 * 4096].reshape(self.n, 5, 16, 16, 16).copy()
 
     def extract(self, tau):
-        ws = np.zeros(self.lib.gof_tsdf_extract_ws_bytes(self.n), np.uint8)
+        ws = _buf("extract ws", self.lib.gof_tsdf_extract_ws_bytes(self.n), np.uint8)
         nv, nt = C.c_int64(), C.c_int64()
         self._check(self.lib.gof_tsdf_extract_count(C.byref(self.vol), self.n, tau, _p(ws), ws.size, C.byref(nv), C.byref(nt), None))
         V, F = nv.value, nt.value
-        out = [np.zeros((V, 3), np.float32), np.zeros((F, 3), np.int32), np.zeros((V, 3), np.float32), np.zeros((V, 3), np.float32)]
+        out = [_written((V, 3), np.float32), _written((F, 3), np.int32), _written((V, 3), np.float32), _written((V, 3), np.float32)]
         self._check(self.lib.gof_tsdf_extract_emit(C.byref(self.vol), self.n, tau, _p(ws), ws.size, V, F, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), None))
         return out
 
 
-def scene_inputs(name):
+def scene_inputs(name, voxel=None):
     W, H, nv, v = EMU_SCENES[name] if name in EMU_SCENES else LARGE_SCENES[name]
+    v = voxel or v
     K = T.intrinsic(W, H)
     views = []
     for E in T.ring_views(nv, seed=len(name)):
@@ -128,7 +168,19 @@ def scene_inputs(name):
 
 def run_emulated(name, out):
     """child process: every frame's block set (a one-frame volume each), the fused volume and its mesh -> npz"""
+    global _fill, _recording
     lib = _emu_lib()
+    _fill = os.environ.get("GOF_TSDF_FILL", "zero")
+    assert _fill in FILLS, _fill
+    if _fill == "stale":          # the larger volume first: fused and extracted on 0xA5 buffers, which then are what it left behind
+        _fill, _recording = "0xA5", True
+        dviews, dv = scene_inputs(*STALE_DONOR)
+        donor = EmuVolume(lib, dv)
+        for d, c, K, E in dviews:
+            donor.integrate(d, c, K, E)
+        donor.extract(TAU)
+        _left.update({k: a.copy() for k, a in _left.items()})
+        _fill, _recording = "stale", False
     views, v = scene_inputs(name)
     res = {}
     for i, (d, c, K, E) in enumerate(views):
@@ -140,12 +192,14 @@ def run_emulated(name, out):
         vol.integrate(d, c, K, E)
     res["coords"], res["data"] = vol.blocks()
     res["V"], res["F"], res["C"], res["N"] = vol.extract(TAU)
+    if _fill == "stale":
+        assert donor.n > vol.n and donor.vol.table_capacity >= vol.vol.table_capacity, "the stale policy's donor volume is not the larger one"
     np.savez(out, **res)
 
 
-def _emulate(name, tmp_path, order=None):
-    out = str(tmp_path / ("%s_%s.npz" % (name, (order or "forward").replace(":", "_"))))
-    env = dict(os.environ)
+def _emulate(name, tmp_path, order=None, fill="zero"):
+    out = str(tmp_path / ("%s_%s_%s.npz" % (name, (order or "forward").replace(":", "_"), fill)))
+    env = dict(os.environ, GOF_TSDF_FILL=fill)
     if order:
         env["HIPEMU_ORDER"] = order
     r = subprocess.run([sys.executable, os.path.abspath(__file__), name, out], env=env, capture_output=True, text=True, timeout=900)
@@ -206,6 +260,31 @@ def check_against_restatement(name, res):
 def test_emulated_kernels_match_restatement(name, tmp_path):
     _needs_emulator()
     check_against_restatement(name, _emulate(name, tmp_path))
+
+
+_zero_filled = {}
+
+
+@pytest.mark.parametrize("fill", FILLS[1:])
+@pytest.mark.parametrize("name", sorted(EMU_SCENES))
+def test_emulated_kernels_do_not_depend_on_what_their_buffers_held(name, fill, tmp_path):
+    """the volume's arrays (gof_tsdf_grow's destination), the frame and the extract workspace filled with 0xA5, with 0xFF, or left over
+    from a larger volume: the same comparison with the restatement, and every bit of the run on cleared buffers (blocks in key order)"""
+    _needs_emulator()
+    got = _emulate(name, tmp_path, fill=fill)
+    check_against_restatement(name, got)
+    if name not in _zero_filled:
+        _zero_filled[name] = _emulate(name, tmp_path)
+    want = _zero_filled[name]
+    assert sorted(got) == sorted(want)
+    for k in want:
+        if k.startswith("frame"):          # (a frame's block set: its storage order is the order the allocating lanes arrived in)
+            assert np.array_equal(np.sort(T.pack(got[k])), np.sort(T.pack(want[k]))), k
+        elif k not in ("coords", "data"):
+            assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and got[k].tobytes() == want[k].tobytes(), k
+    kg, kw = T.pack(got["coords"]), T.pack(want["coords"])
+    assert np.array_equal(np.sort(kg), np.sort(kw))
+    assert got["data"][np.argsort(kg)].tobytes() == want["data"][np.argsort(kw)].tobytes()
 
 
 @pytest.mark.parametrize("order", ["reverse", "random:7"])
