@@ -39,6 +39,11 @@ What it does, in this order (nothing in the reference checkout is edited):
   8. given eval_tnt/run.py (Open3D 0.9: the last step of scripts/run_tnt.py), the launcher runs tnt_eval's command line (the HIP
      Tanks-and-Temples F-score evaluation, csrc/cloud_reg.hip) with the same arguments; GOF_TNT_EVAL_SUBPROCESS=1 leaves the script
      alone.
+  9. evaluate_dtu_mesh.py:59-131, 172 asks cv2, scikit-image and trimesh for the calibration decomposition, the mask dilation, the
+     projection of all vertices into all views and the mesh container: the script's `cull_mesh` becomes mesh_cull.cull_mesh (the HIP
+     mesh culling, csrc/mesh_cull.hip), and where cv2 / trimesh are not installed its `load_dtu_camera` becomes
+     mesh_cull.load_dtu_camera and its `trimesh` a namespace whose load() is mesh_cull.load; import stand-ins for the packages that
+     are missing (shims_dtu/) go LAST on sys.path, for this script only.  GOF_DTU_CULL_TORCH=1 leaves the script alone.
 """
 import importlib
 import os
@@ -177,6 +182,71 @@ def dtu_eval_rebinding(script):
     return {"os": _OsWithInProcessEval()}
 
 
+_DTU_PACKAGES = ("trimesh", "skimage", "cv2")
+
+
+def _is_dtu_script(script):
+    return os.path.basename(script) == "evaluate_dtu_mesh.py" and os.environ.get("GOF_DTU_CULL_TORCH", "0") != "1"
+
+
+def _importable(name):
+    import importlib.util
+    shim = os.path.join(PKG, "shims_dtu")
+    try:
+        spec = importlib.util.find_spec(name)
+    except (ImportError, ValueError):
+        return False
+    return spec is not None and not (spec.origin or "").startswith(shim)
+
+
+def _cull_mesh(cameras, mesh):
+    import mesh_cull
+    return mesh_cull.cull_mesh(cameras, mesh)
+
+
+def _load_dtu_camera(DTU):
+    import mesh_cull
+    return mesh_cull.load_dtu_camera(DTU)
+
+
+class _TrimeshNamespace:
+    """`trimesh` for evaluate_dtu_mesh.py where trimesh is not installed: load() reads the mesh onto the device (mesh_cull.load), any
+    other attribute is the import stand-in's (which raises when called)."""
+
+    @staticmethod
+    def load(path, *a, **k):
+        import mesh_cull
+        return mesh_cull.load(path)
+
+    def __getattr__(self, name):
+        return getattr(importlib.import_module("trimesh"), name)
+
+
+def dtu_cull_rebinding(script):
+    """the names to replace in `script`'s namespace for the DTU mesh culling: for evaluate_dtu_mesh.py `cull_mesh` always,
+    `load_dtu_camera` where cv2 is missing, `trimesh` where trimesh is missing.  The replacements import mesh_cull when they are
+    called, not here."""
+    if not _is_dtu_script(script):
+        return {}
+    rebind = {"cull_mesh": _cull_mesh}
+    if not _importable("cv2"):
+        rebind["load_dtu_camera"] = _load_dtu_camera
+    if not _importable("trimesh"):
+        rebind["trimesh"] = _TrimeshNamespace()
+    return rebind
+
+
+def add_dtu_shims(script):
+    """for evaluate_dtu_mesh.py: the import stand-ins of the packages that are not installed, appended to sys.path (an installed
+    package wins; no other script's imports change)"""
+    if not _is_dtu_script(script):
+        return
+    for name in _DTU_PACKAGES:
+        shim = os.path.join(PKG, "shims_dtu", name)
+        if not _importable(name) and shim not in sys.path:
+            sys.path.append(shim)
+
+
 def _tnt_eval_main(argv):
     import tnt_eval
     return tnt_eval.main(argv)
@@ -214,6 +284,7 @@ def main():
             shim = os.path.join(PKG, "shims")
             if shim not in sys.path:
                 sys.path.append(shim)
+    add_dtu_shims(script)
     import diff_gaussian_rasterization  # noqa: F401  fail early and loudly if libgof_hip.so is missing
     if os.environ.get("GOF_STATS_JSON"):
         # the binding's counters of the whole run (frames redone for a pool / capacity learnt too small, read-backs, shapes that inherited
@@ -252,6 +323,7 @@ def main():
     import tsdf_fusion
     rebind["tsdf_fusion"] = tsdf_fusion.tsdf_fusion
     rebind.update(dtu_eval_rebinding(script))
+    rebind.update(dtu_cull_rebinding(script))
     run_script(script, rebind)
 
 

@@ -1,0 +1,416 @@
+"""Mesh culling of the DTU evaluation on the GPU: the reference's evaluate_dtu_mesh.py:59-131 without trimesh, scikit-image and cv2.
+
+    packed = dilate_mask(mask, r)                          # :114-115  binary_dilation(mask / 256., disk(6)), bit-packed
+    keep = cull_vertices(vertices, views)                  # :105-126  every vertex against every view's dilated mask
+    out = compact_mesh(keep, faces, attrs)                 # :127-130  update_vertices / update_faces
+    mesh = load(path); mesh = cull_mesh(cameras, mesh); mesh.export(path)       # trimesh.load, the script's cull_mesh, .export
+    poses = load_dtu_camera(DTU)                           # :59-75    cv2.decomposeProjectionMatrix
+
+The kernels are ``gof_mesh_*`` of libgof_hip.so (csrc/mesh_cull.hip, include/gof_mesh_hip.h); the contract is DESIGN.md §3.10: tensors
+on a ROCm device in and out, results bit-equal to numpy's.  There is no host fallback: host tensors are refused.  Two stated
+deviations: the keep / drop decisions are made in fp64 instead of fp32 GEMMs, and the world-to-camera matrix itself
+is used instead of the script's fp32 inverse of its inverse.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from diff_gaussian_rasterization import _backend as B
+import mesh_eval
+
+__all__ = ["dilate_mask", "cull_vertices", "compact_mesh", "last_stats", "view_matrix", "DeviceMesh", "load", "cull_mesh",
+           "load_dtu_camera", "decompose_projection_matrix", "GofCullView"]
+
+lib = B.lib
+_vp, _sz, _i64, _i32 = C.c_void_p, C.c_size_t, C.c_int64, C.c_int32
+_P64 = C.POINTER(C.c_int64)
+
+
+class GofCullView(C.Structure):
+    """Mirror of ``GofCullView`` in include/gof_mesh_hip.h."""
+    _fields_ = [("m", C.c_double * 12), ("W", C.c_int32), ("H", C.c_int32), ("mask_offset", C.c_int64), ("row_words", C.c_int64)]
+
+
+_VIEW_DTYPE = np.dtype([("m", "<f8", (12,)), ("W", "<i4"), ("H", "<i4"), ("mask_offset", "<i8"), ("row_words", "<i8")])
+assert _VIEW_DTYPE.itemsize == C.sizeof(GofCullView) == 120
+
+lib.gof_mesh_mask_row_words.restype = _i64
+lib.gof_mesh_mask_row_words.argtypes = [_i32]
+lib.gof_mesh_cull_ws_bytes.restype = _sz
+lib.gof_mesh_cull_ws_bytes.argtypes = [_i64]
+lib.gof_mesh_compact_ws_bytes.restype = _sz
+lib.gof_mesh_compact_ws_bytes.argtypes = [_i64, _i64]
+lib.gof_densify_ws_bytes.restype = _sz
+lib.gof_densify_ws_bytes.argtypes = [_i64]
+for _name, _args in {
+        "gof_mesh_dilate": [_i32, _i32, _vp, _i32, _i32, _vp, _vp],
+        "gof_mesh_cull": [_i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
+        "gof_mesh_compact": [_i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _P64, _vp],
+        "gof_compact_rows": [_i64, _vp, _vp, _vp, _vp, _sz, _P64, _vp],
+        "gof_rows_gather": [_i64, _i32, _vp, _vp, _vp, _vp, _vp]}.items():
+    getattr(lib, _name).restype = C.c_int
+    getattr(lib, _name).argtypes = _args
+
+MAX_RADIUS = 31
+_last = {}
+
+
+def last_stats():
+    """Statistics of the last dilate_mask / cull_vertices / compact_mesh calls (one sub-dictionary each): sizes, counts, workspace bytes."""
+    return {k: dict(v) for k, v in _last.items()}
+
+
+def _stream():
+    return B._stream()
+
+
+def _device_of(t):
+    return torch.cuda.device(t.device)
+
+
+def _on_device(t):
+    return t.device.type == "cuda"
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("mesh_cull (gfx950 backend) needs a ROCm device")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _tensor(t, who, what, dtypes, cols=None):
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError("%s: %s must be a torch tensor" % (who, what))
+    if not _on_device(t):
+        raise RuntimeError("%s (gfx950 backend) needs %s on a ROCm device, got %s" % (who, what, t.device))
+    if t.dtype not in dtypes:
+        raise RuntimeError("%s: %s must be %s, got %s" % (who, what, " or ".join(str(d) for d in dtypes), t.dtype))
+    if cols is not None and (t.dim() != 2 or t.size(1) != cols):
+        raise RuntimeError("%s: %s must have dimensions (N, %d)" % (who, what, cols))
+    if t.size(0) >= 2 ** 31 - 1:
+        raise RuntimeError("%s: at most 2^31 - 2 rows" % who)
+    return t.contiguous()
+
+
+# ---- (a) ----------------------------------------------------------------------------------------------------------------------------
+def mask_row_words(W):
+    return (int(W) + 63) // 64
+
+
+def dilate_mask(mask, r=6, out=None):
+    """evaluate_dtu_mesh.py:114-115: mask (H,W) float32 or uint8 on a ROCm device; a pixel is set iff mask / 256. != 0 ->
+    (H, ceil(W/64)) int64 there: bit x % 64 of word x // 64 of row y = the disk dilation of radius r at (y, x); pad bits zero.
+    `out`: a contiguous int64 tensor of that many words to write into."""
+    m = _tensor(mask, "dilate_mask", "mask", (torch.float32, torch.uint8))
+    if m.dim() != 2 or m.numel() == 0:
+        raise RuntimeError("dilate_mask: mask must have dimensions (H, W), both at least 1")
+    r = int(r)
+    if not 0 <= r <= MAX_RADIUS:
+        raise ValueError("dilate_mask: the radius must lie in [0, %d], got %d" % (MAX_RADIUS, r))
+    H, W = int(m.size(0)), int(m.size(1))
+    nw = mask_row_words(W)
+    with _device_of(m):
+        if out is None:
+            out = torch.empty((H, nw), dtype=torch.int64, device=m.device)
+        elif out.dtype != torch.int64 or out.numel() != H * nw or not out.is_contiguous() or out.device != m.device:
+            raise RuntimeError("dilate_mask: out must be a contiguous int64 tensor of %d words on the mask's device" % (H * nw))
+        B._check(lib.gof_mesh_dilate(W, H, m.data_ptr(), 1 if m.dtype == torch.uint8 else 0, r, out.data_ptr(), _stream()))
+    _last["dilate"] = {"width": W, "height": H, "radius": r, "row_words": nw}
+    return out.view(H, nw)
+
+
+# ---- (b) ----------------------------------------------------------------------------------------------------------------------------
+def view_matrix(focal_x, focal_y, W, H, world_view_transform):
+    """m (3,4) float64 = rows 0..2 of K W2C: K = the script's intrinsic (:94-98: focal_x, focal_y, W / 2., H / 2. stored in a float32
+    matrix), W2C = world_view_transform.T in float32.  K has two entries per row: the product is written out, no BLAS."""
+    wvt = world_view_transform
+    if isinstance(wvt, torch.Tensor):
+        wvt = wvt.detach().cpu().numpy()
+    w2c = np.asarray(wvt, np.float32).reshape(4, 4).T.astype(np.float64)
+    fx, fy, cx, cy = (float(np.float32(v)) for v in (focal_x, focal_y, W / 2.0, H / 2.0))
+    return np.stack([fx * w2c[0] + cx * w2c[2], fy * w2c[1] + cy * w2c[2], w2c[2]])
+
+
+def cull_vertices(vertices, views):
+    """evaluate_dtu_mesh.py:105-126 in one launch: vertices (NV,3) float32 on a ROCm device; views: a sequence of (m, W, H, packed)
+    with m (3,4) float64 (view_matrix) and packed = dilate_mask's result for that view -> keep (NV,) bool there: no view drops it."""
+    v = _tensor(vertices, "cull_vertices", "vertices", (torch.float32,), 3)
+    nv, n = int(v.size(0)), len(views)
+    rec = np.zeros(n, _VIEW_DTYPE)
+    packed, off = [], 0
+    for i, (m, W, H, p) in enumerate(views):
+        p = _tensor(p, "cull_vertices", "a packed mask", (torch.int64,))
+        if p.device != v.device:
+            raise RuntimeError("cull_vertices: vertices and masks are on different devices")
+        W, H = int(W), int(H)
+        if W < 1 or H < 1 or p.numel() != H * mask_row_words(W):
+            raise RuntimeError("cull_vertices: view %d: a mask of %d words for an image of %d x %d" % (i, p.numel(), W, H))
+        rec[i] = (np.asarray(m, np.float64).reshape(12), W, H, off, mask_row_words(W))
+        packed.append(p.reshape(-1))
+        off += p.numel()
+    with _device_of(v):
+        if n == 0:
+            masks = None
+        elif n == 1 or all(packed[i].data_ptr() == packed[0].data_ptr() + 8 * int(rec["mask_offset"][i]) for i in range(n)):
+            masks = packed[0]                 # (cull_mesh dilates into one buffer: nothing to copy)
+        else:
+            masks = torch.cat(packed)
+        records = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(v.device) if n else None
+        nb = lib.gof_mesh_cull_ws_bytes(nv)
+        ws = torch.empty(nb, dtype=torch.uint8, device=v.device)
+        keep = torch.empty(nv, dtype=torch.uint8, device=v.device)
+        B._check(lib.gof_mesh_cull(nv, _ptr(v), n, _ptr(records), _ptr(masks), off, _ptr(keep), ws.data_ptr(), nb, _stream()))
+    _last["cull"] = {"vertices": nv, "views": n, "mask_words": int(off), "workspace_bytes": int(nb)}
+    return keep.bool()
+
+
+# ---- (c) ----------------------------------------------------------------------------------------------------------------------------
+def _gather(rows, t):
+    """t[rows] for a 2-D tensor whose rows are whole 4-byte words, through gof_rows_gather (the bytes travel as float32 words)"""
+    n = int(rows.numel())
+    src = t.contiguous()
+    if n == 0:
+        return torch.empty((0, int(src.size(1))), dtype=src.dtype, device=src.device)
+    words = src.view(torch.float32) if src.dtype != torch.float32 else src
+    per = int(words.size(1))
+    out = torch.empty((n, per), dtype=torch.float32, device=t.device)
+    if n:
+        B._check(lib.gof_rows_gather(n, per, rows.data_ptr(), words.data_ptr(), None, out.data_ptr(), _stream()))
+    return out.view(t.dtype) if t.dtype != torch.float32 else out
+
+
+def compact_mesh(keep, faces, attrs=(), drop_faces=True):
+    """evaluate_dtu_mesh.py:127-130: keep (NV,) bool / uint8, faces (NF,3) int32, attrs: 2-D tensors of NV rows (whole 4-byte words per
+    row), all on one ROCm device -> dict(rows (K,) int32: the kept vertices in order; attrs: their rows; face_keep (NF,) bool: all
+    three vertices kept; faces (M,3) int32: drop_faces: the kept faces renumbered, else every face with removed vertices -> 0)."""
+    k = _tensor(keep, "compact_mesh", "keep", (torch.bool, torch.uint8))
+    k = k.view(torch.uint8) if k.dtype == torch.bool else k
+    f = _tensor(faces, "compact_mesh", "faces", (torch.int32,), 3)
+    if k.dim() != 1 or f.device != k.device:
+        raise RuntimeError("compact_mesh: keep must be (NV,) and on the faces' device")
+    nv, nf = int(k.numel()), int(f.size(0))
+    for a in attrs:
+        if a.dim() != 2 or a.size(0) != nv or a.device != k.device or (a.size(1) * a.element_size()) % 4:
+            raise RuntimeError("compact_mesh: an attribute must be (NV, C) with whole 4-byte words per row, on keep's device")
+    with _device_of(k):
+        nb = lib.gof_mesh_compact_ws_bytes(nv, nf)
+        ws = torch.empty(nb, dtype=torch.uint8, device=k.device)
+        rows = torch.empty(nv, dtype=torch.int32, device=k.device)
+        out_faces = torch.empty((nf, 3), dtype=torch.int32, device=k.device)
+        face_keep = torch.empty(nf, dtype=torch.uint8, device=k.device)
+        counts = (C.c_int64 * 2)()
+        B._check(lib.gof_mesh_compact(nv, _ptr(k), nf, _ptr(f), 1 if drop_faces else 0, _ptr(rows), _ptr(out_faces), _ptr(face_keep),
+                                      ws.data_ptr(), nb, counts, _stream()))
+        rows = rows[:counts[0]]
+        out = {"rows": rows, "faces": out_faces[:counts[1]], "face_keep": face_keep.bool(), "attrs": [_gather(rows, a) for a in attrs]}
+    _last["compact"] = {"vertices": nv, "faces": nf, "kept_vertices": int(counts[0]), "kept_faces": int(counts[1]), "workspace_bytes": int(nb)}
+    return out
+
+
+def _compact_rows(keep_u8):
+    """(N,) uint8 -> the indices of its non-zero entries, in order (gof_compact_rows)"""
+    n = int(keep_u8.numel())
+    nb = lib.gof_densify_ws_bytes(n)
+    ws = torch.empty(nb, dtype=torch.uint8, device=keep_u8.device)
+    out = torch.empty(n, dtype=torch.int32, device=keep_u8.device)
+    cnt = C.c_int64()
+    B._check(lib.gof_compact_rows(n, _ptr(keep_u8), None, _ptr(out), ws.data_ptr(), nb, C.byref(cnt), _stream()))
+    return out[:cnt.value]
+
+
+# ---- the mesh object -----------------------------------------------------------------------------------------------------------------
+class DeviceMesh:
+    """What evaluate_dtu_mesh.py asks of a trimesh.Trimesh, with the arrays on the device: vertices fp64 (N,3), faces int32 (M,3),
+    optional normals float32 (N,3) and colours uint8 (N,4: red green blue + a pad byte, one 4-byte word per vertex)."""
+
+    def __init__(self, vertices, faces, normals=None, colors=None, device=None):
+        self.device = torch.device(device) if device is not None else _device()
+        self._v = self._up(np.ascontiguousarray(vertices, np.float64).reshape(-1, 3))
+        self._f = self._up(np.ascontiguousarray(faces, np.int32).reshape(-1, 3))
+        self._n = self._c = None
+        n = int(self._v.size(0))
+        if normals is not None:
+            self._n = self._up(np.ascontiguousarray(normals, np.float32).reshape(n, 3))
+        if colors is not None:
+            c = np.zeros((n, 4), np.uint8)
+            c[:, :3] = np.asarray(colors, np.uint8).reshape(n, -1)[:, :3]
+            self._c = self._up(c)
+
+    def _up(self, a):
+        return torch.from_numpy(a).to(self.device)
+
+    def _mask(self, mask, n, who):
+        m = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask, bool)))
+        if m.dtype not in (torch.bool, torch.uint8) or m.dim() != 1 or m.numel() != n:
+            raise ValueError("%s: the mask must be boolean with %d entries" % (who, n))
+        m = m.to(self.device).contiguous()
+        return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+    # trimesh's getters return host arrays: the script's `mesh.vertices * s` and `@ r.T + t` run in numpy, bit for bit as with trimesh
+    @property
+    def vertices(self):
+        return self._v.cpu().numpy()
+
+    @vertices.setter
+    def vertices(self, value):
+        a = np.ascontiguousarray(value, np.float64)
+        if a.shape != tuple(self._v.shape):
+            raise ValueError("DeviceMesh.vertices: expected %s, got %s" % (tuple(self._v.shape), a.shape))
+        self._v = self._up(a)
+
+    @property
+    def faces(self):
+        return self._f.cpu().numpy()
+
+    @property
+    def vertex_normals(self):
+        return None if self._n is None else self._n.cpu().numpy()
+
+    @property
+    def vertex_colors(self):
+        return None if self._c is None else self._c.cpu().numpy()[:, :3]
+
+    def _attrs(self):
+        return [a for a in (self._v, self._n, self._c) if a is not None]
+
+    def _set_attrs(self, new):
+        it = iter(new)
+        self._v = next(it)
+        if self._n is not None:
+            self._n = next(it)
+        if self._c is not None:
+            self._c = next(it)
+
+    def _apply(self, keep_u8, drop_faces):
+        out = compact_mesh(keep_u8, self._f, self._attrs(), drop_faces=drop_faces)
+        self._set_attrs(out["attrs"])
+        self._f = out["faces"].contiguous()
+
+    def update_vertices(self, mask):
+        """trimesh's: keep vertices[mask] and renumber the faces (the index of a removed vertex becomes 0: update_faces removes those)"""
+        self._apply(self._mask(mask, int(self._v.size(0)), "update_vertices"), False)
+
+    def update_faces(self, mask):
+        """trimesh's: keep faces[mask]"""
+        m = self._mask(mask, int(self._f.size(0)), "update_faces")
+        with _device_of(m):
+            self._f = _gather(_compact_rows(m), self._f)
+
+    def export(self, path):
+        """binary little-endian PLY: float x y z [nx ny nz] [uchar red green blue], `list uchar int` faces"""
+        v = self._v.cpu().numpy()
+        fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+        head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(v)
+        if self._n is not None:
+            fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+            head += "property float nx\nproperty float ny\nproperty float nz\n"
+        if self._c is not None:
+            fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+            head += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        f = self._f.cpu().numpy()
+        head += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(f)
+        rec = np.zeros(len(v), fields)
+        n = None if self._n is None else self._n.cpu().numpy()
+        c = None if self._c is None else self._c.cpu().numpy()
+        for i, k in enumerate("xyz"):
+            rec[k] = v[:, i].astype(np.float32)
+            if n is not None:
+                rec["n" + k] = n[:, i]
+        if c is not None:
+            for i, k in enumerate(("red", "green", "blue")):
+                rec[k] = c[:, i]
+        fr = np.zeros(len(f), [("n", "u1"), ("i", "<i4", (3,))])
+        fr["n"], fr["i"] = 3, f
+        with open(path, "wb") as fh:
+            fh.write(head.encode("ascii"))
+            fh.write(rec.tobytes())
+            fh.write(fr.tobytes())
+
+
+def load(path, device=None):
+    """trimesh.load for the PLY files of this pipeline (tsdf_fusion.write_ply: float x y z nx ny nz, uchar red green blue, triangle
+    faces; ASCII and double coordinates as mesh_eval.read_ply reads them) -> DeviceMesh"""
+    el = mesh_eval.read_ply_elements(path)
+    rec = el["vertex"]
+    names = rec.dtype.names
+    v = np.stack([rec["x"], rec["y"], rec["z"]], axis=-1).astype(np.float64)
+    normals = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=-1).astype(np.float32) if all(k in names for k in ("nx", "ny", "nz")) else None
+    colors = np.stack([rec["red"], rec["green"], rec["blue"]], axis=-1).astype(np.uint8) if all(k in names for k in ("red", "green", "blue")) else None
+    faces = np.zeros((0, 3), np.int32)
+    if "face" in el and "_i" in (el["face"].dtype.names or ()):
+        faces = el["face"]["_i"].astype(np.int32).reshape(-1, 3)
+    return DeviceMesh(v, faces, normals, colors, device=device)
+
+
+# ---- the script's functions ----------------------------------------------------------------------------------------------------------
+def cull_mesh(cameras, mesh, radius=6):
+    """evaluate_dtu_mesh.py:77-139, a drop-in: every camera's gt_alpha_mask dilated on the device into one buffer, one culling launch
+    over all views, the mesh compacted.  A DeviceMesh stays on the device; any other mesh object (a trimesh.Trimesh) gets the two
+    masks through its own update_vertices / update_faces."""
+    dev = mesh.device if isinstance(mesh, DeviceMesh) else _device()
+    sizes = []
+    for i, cam in enumerate(cameras):
+        if getattr(cam, "gt_alpha_mask", None) is None:
+            raise ValueError("cull_mesh: camera %d (%s) has no gt_alpha_mask: the culling needs every view's object mask "
+                             "(DTU scenes carry it in the alpha channel of their images)" % (i, getattr(cam, "image_name", "?")))
+        sizes.append((int(cam.image_width), int(cam.image_height)))
+    words = [H * mask_row_words(W) for W, H in sizes]
+    with torch.no_grad():
+        buf = torch.empty(int(sum(words)), dtype=torch.int64, device=dev)
+        views, off = [], 0
+        for cam, (W, H), n in zip(cameras, sizes, words):
+            m = torch.as_tensor(cam.gt_alpha_mask)[0].detach().to(dev)
+            if m.dtype not in (torch.float32, torch.uint8):
+                m = m.float()
+            if tuple(m.shape) != (H, W):
+                raise ValueError("cull_mesh: a mask of %s for an image of %d x %d" % (tuple(m.shape), W, H))
+            p = dilate_mask(m.contiguous(), radius, out=buf[off:off + n])
+            views.append((view_matrix(cam.focal_x, cam.focal_y, W, H, cam.world_view_transform), W, H, p))
+            off += n
+        if isinstance(mesh, DeviceMesh):
+            keep = cull_vertices(mesh._v.float(), views)
+            mesh._apply(keep.view(torch.uint8), True)
+            return mesh
+        v32 = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.vertices), np.float32).reshape(-1, 3)).to(dev)
+        f32 = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.faces), np.int32).reshape(-1, 3)).to(dev)
+        keep = cull_vertices(v32, views)
+        out = compact_mesh(keep, f32)
+    mesh.update_vertices(keep.cpu().numpy())
+    mesh.update_faces(out["face_keep"].cpu().numpy())
+    return mesh
+
+
+def decompose_projection_matrix(P):
+    """P (3,4) = K [R | -R C] -> (K (3,3) upper triangular with a positive diagonal, K[2,2] = 1; R (3,3); C (3,)) in fp64: the RQ
+    decomposition of P[:, :3] through numpy's QR, and the camera centre C = -P[:, :3]^-1 P[:, 3].  The centre is the contract (it is
+    all evaluate_dtu_mesh.py reads); R's sign convention follows from the positive diagonal and is not pinned to OpenCV's."""
+    P = np.asarray(P, np.float64).reshape(3, 4)
+    M = P[:, :3]
+    J = np.eye(3)[::-1]
+    q, r = np.linalg.qr((J @ M).T)
+    K = J @ r.T @ J
+    R = J @ q.T
+    s = np.sign(np.diag(K))
+    s[s == 0] = 1.0
+    K, R = K * s[None, :], R * s[:, None]
+    centre = -np.linalg.solve(M, P[:, 3])
+    return K / K[2, 2], R, centre
+
+
+def load_dtu_camera(DTU):
+    """evaluate_dtu_mesh.py:59-75 without cv2: the 64 calibration matrices -> [pose (3,4) float32: R^T | centre]"""
+    poses = []
+    for i in range(1, 64 + 1):
+        projection = np.loadtxt(os.path.join(DTU, "Calibration/cal18/pos_%03d.txt" % i), dtype=np.float32)
+        _, R, centre = decompose_projection_matrix(projection)
+        pose = np.eye(4, dtype=np.float32)
+        pose[:3, :3] = R.transpose()
+        pose[:3, 3] = centre
+        poses.append(pose[:3])
+    return poses

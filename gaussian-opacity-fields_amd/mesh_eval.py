@@ -22,7 +22,7 @@ import torch
 
 from diff_gaussian_rasterization import _backend as B
 
-__all__ = ["sample_mesh", "thin", "nearest", "last_stats", "dtu_chamfer", "read_ply", "write_vis_ply", "main"]
+__all__ = ["sample_mesh", "thin", "nearest", "last_stats", "dtu_chamfer", "read_ply", "read_ply_elements", "write_vis_ply", "main"]
 
 lib = B.lib
 _vp, _sz, _i64, _f64 = C.c_void_p, C.c_size_t, C.c_int64, C.c_double
@@ -195,9 +195,9 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply(path):
-    """A small PLY reader (binary little-endian and ASCII): -> (vertices (N,3) float64, triangles (M,3) int32 or None).  float / double
-    coordinates; other vertex properties (colours, normals) are skipped; faces must be triangles."""
+def read_ply_elements(path):
+    """The parser behind read_ply (and mesh_cull.load): -> {element name: numpy record array}, one field per property; the list
+    property of a face element becomes the fields "_n" (the counts) and "_i" ((M,3) indices: faces must be triangles)."""
     with open(path, "rb") as f:
         raw = f.read()
     end = raw.find(b"end_header")
@@ -219,7 +219,7 @@ def read_ply(path):
         raise ValueError("%s: PLY format %r is not supported (binary_little_endian, ascii)" % (path, fmt))
     tokens = raw[body:].split() if fmt == "ascii" else None
     pos = 0 if fmt == "ascii" else body
-    vertices = triangles = None
+    out = {}
     for name, count, props in elements:
         lists = [p for p in props if p[1][0] == "list"]
         fields = []
@@ -247,14 +247,23 @@ def read_ply(path):
         else:
             rec = np.frombuffer(raw, dtype=dt, count=count, offset=pos)
             pos += count * dt.itemsize
-        if name == "vertex":
-            vertices = np.stack([rec["x"], rec["y"], rec["z"]], axis=-1).astype(np.float64)
-        elif name == "face" and lists:
-            if count and not (rec["_n"] == 3).all():
-                raise ValueError("%s: only triangles are supported" % path)
-            triangles = np.ascontiguousarray(rec["_i"].astype(np.int32)).reshape(-1, 3)
-    if vertices is None:
+        if name == "face" and lists and count and not (rec["_n"] == 3).all():
+            raise ValueError("%s: only triangles are supported" % path)
+        out[name] = rec
+    if "vertex" not in out:
         raise ValueError("%s: no vertex element" % path)
+    return out
+
+
+def read_ply(path):
+    """A small PLY reader (binary little-endian and ASCII): -> (vertices (N,3) float64, triangles (M,3) int32 or None).  float / double
+    coordinates; other vertex properties (colours, normals) are skipped; faces must be triangles."""
+    el = read_ply_elements(path)
+    rec = el["vertex"]
+    vertices = np.stack([rec["x"], rec["y"], rec["z"]], axis=-1).astype(np.float64)
+    triangles = None
+    if "face" in el and "_i" in (el["face"].dtype.names or ()):
+        triangles = np.ascontiguousarray(el["face"]["_i"].astype(np.int32)).reshape(-1, 3)
     return np.ascontiguousarray(vertices), triangles
 
 
