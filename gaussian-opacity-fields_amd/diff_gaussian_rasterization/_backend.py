@@ -258,6 +258,15 @@ USAGE_WORDS = 66        # GOF_USAGE_WORDS (include/gof_hip.h)
 _stats = {"fused_redone_frames": 0, "last_num_rendered": 0, "mask_pool_redone_frames": 0, "record_pool_redone_backwards": 0,
           "backward_queries": 0, "two_stage_frames": 0, "inherited_shapes": 0, "forwards": 0, "backwards": 0}      # bench.py reads these (no effect on the path)
 _recent_P = {}          # (device, W, H) -> P of the latest frame at that resolution
+_sized_for = ({}, {}, {})   # beside _capacity / _mask_need / _staged_need: shape -> the P an INHERITED value was last scaled for (absent: learnt at its own P)
+
+
+def _learn(which, shape_key, value):
+    """a frame of this shape measured that it needs `value`: raise the learnt figure (never lower it); a raised figure is sized for this P"""
+    d = (_capacity, _mask_need, _staged_need)[which]
+    if shape_key not in d or value > d[shape_key]:
+        d[shape_key] = value
+        _sized_for[which].pop(shape_key, None)
 
 
 def _inherit_learnt(shape_key):
@@ -266,7 +275,10 @@ def _inherit_learnt(shape_key):
     next views.  A new P at a resolution whose previous frames had between half and twice as many Gaussians INHERITS what those
     frames learnt -- instance capacity, mask sub-chunks, staged records -- scaled by the growth (never down: a capacity above the
     count costs nothing); the pools are verified per frame as ever, so a guess that turns out too small costs one
-    redone frame.  The old shape's entries are dropped (P changes for good in training; the dicts stay bounded)."""
+    redone frame.  The old shape's entries are dropped (P changes for good in training; the dicts stay bounded).
+    The growth is measured from the P the value was last SIZED for (_sized_for), not from the previous P: a value that came down
+    unchanged from 1.0 M to 0.7 M Gaussians is still sized for 1.0 M and returns to 1.0 M unchanged -- densify up / prune after every
+    opacity reset, or a viewer alternating two checkpoints, would otherwise multiply it by 1.43 on every round trip."""
     dev, P, W, H = shape_key
     prev = _recent_P.get((dev, W, H))
     _recent_P[(dev, W, H)] = P
@@ -275,11 +287,19 @@ def _inherit_learnt(shape_key):
     old = (dev, prev, W, H)
     if old not in _capacity or not (0.5 * prev <= P <= 2.0 * prev):
         return
-    grow = max(1.0, P / float(prev))
-    _capacity[shape_key] = (int(_capacity.pop(old) * grow) + 0xFFFF) & ~0xFFFF
-    for d in (_mask_need, _staged_need):
-        if old in d:
-            d[shape_key] = int(d.pop(old) * grow) + 1
+    for which, d in enumerate((_capacity, _mask_need, _staged_need)):
+        if old not in d:
+            continue
+        base = _sized_for[which].pop(old, prev)
+        value = d.pop(old)
+        if P > base:
+            scaled = int(value * (P / float(base)))
+            if which == 0:
+                value = (scaled + 0xFFFF) & ~0xFFFF               # the capacity stays a multiple of 64 Ki instances
+            else:
+                value = scaled + 1
+        d[shape_key] = value
+        _sized_for[which][shape_key] = max(base, P)
     _stats["inherited_shapes"] += 1
 
 
@@ -405,7 +425,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
             if rc == 0:
                 true_r = int(pin[0].item()) & 0xFFFFFFFF
                 if _round_capacity(true_r) > cap:
-                    _capacity[shape_key] = _round_capacity(true_r)        # growing scene: stay ahead of it
+                    _learn(0, shape_key, _round_capacity(true_r))         # growing scene: stay ahead of it
                 _stats["last_num_rendered"] = true_r
                 return NumRendered(true_r, cap, usage), out_color, radii, geom, binning, img
             if rc != GOF_E_CAPACITY:
@@ -419,7 +439,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         _check(lib.gof_forward_render(v.ref(), rendered, _ptr(radii), _ptr(geom), geom.numel(), _ptr(binning), binning.numel(),
                                       _ptr(img), img.numel(), _ptr(out_color), _stream()))
         if use_fused and not prefiltered and not debug:
-            _capacity[shape_key] = max(_capacity.get(shape_key, 0), _round_capacity(rendered))
+            _learn(0, shape_key, _round_capacity(rendered))
         _stats["last_num_rendered"] = int(rendered)
     return NumRendered(rendered), out_color, radii, geom, binning, img
 
@@ -492,8 +512,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _stats["backward_queries"] += 1           # (a synchronising read-back: first frame of a shape, two-stage forward)
                 _check(lib.gof_backward_query(v.ref(), int(R), binningBuffer.numel(), _ptr(imageBuffer), imageBuffer.numel(), q, _stream()))
                 staged, requested, held = int(q[0]), int(q[1]), int(q[2])
-                _mask_need[shape_key] = max(_mask_need.get(shape_key, 0), requested)
-                _staged_need[shape_key] = max(_staged_need.get(shape_key, 0), staged)
+                _learn(1, shape_key, requested)
+                _learn(2, shape_key, staged)
                 if requested > held:
                     raise MaskPoolTooSmall(requested, held)
                 nscratch = lib.gof_backward_scratch_bytes(P, int(R)) if FULL_BACKWARD_SCRATCH else lib.gof_backward_scratch_bytes_for(P, int(R), staged)
@@ -519,8 +539,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 q = (C.c_uint32 * 3)()
                 _check(lib.gof_usage_decode(C.c_void_p(words.data_ptr()), int(R), W, H, binningBuffer.numel(), q))
                 staged, requested, held = int(q[0]), int(q[1]), int(q[2])
-                _mask_need[shape_key] = max(_mask_need.get(shape_key, 0), requested)
-                _staged_need[shape_key] = max(_staged_need.get(shape_key, 0), staged)
+                _learn(1, shape_key, requested)
+                _learn(2, shape_key, staged)
                 if requested > held:                  # masks are missing: the gradients just computed are incomplete -> forward again, then backward
                     if track:
                         # the abandoned backward must not count as a rasterizer backward of this step: the repeated one would make it

@@ -69,8 +69,10 @@ if __name__ == "__main__":
         b = copy.deepcopy(a)
         torch.manual_seed(77)
         ra = ref_method(a, 0.0002, 0.05, 3.0, max_screen)
+        next_a = torch.randn(4, device="cuda")                 # the generator's next draw behind each method
         torch.manual_seed(77)
         rb = T.densify_and_prune(b, 0.0002, 0.05, 3.0, max_screen)
+        next_b = torch.randn(4, device="cuda")
         torch.cuda.synchronize()
         out = {"P": P, "fused_adam": fused, "max_screen_size": max_screen, "n_ref": int(a._xyz.shape[0]), "n_ours": int(b._xyz.shape[0]),
                "ret_ref": [int(x) for x in ra], "ret_ours": [int(x) for x in rb], "next_normal_equal": None, "diff": {}}
@@ -82,6 +84,5 @@ if __name__ == "__main__":
             out["diff"][name + ".is_param_of_optimizer"] = 0.0 if any(grp["params"][0] is getattr(b, attr) for grp in b.optimizer.param_groups) else 1.0
         for name in ("xyz_gradient_accum", "xyz_gradient_accum_abs", "xyz_gradient_accum_abs_max", "denom", "max_radii2D"):
             out["diff"][name] = diff(getattr(a, name), getattr(b, name))
-        out["next_normal_equal"] = True        # both consumed the generator identically iff the next draw matches
-        torch.manual_seed(77)
+        out["next_normal_equal"] = bool(torch.equal(next_a, next_b))        # both consumed the generator identically iff the next draw matches
         print(json.dumps(out), flush=True)

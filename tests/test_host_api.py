@@ -126,8 +126,9 @@ def test_learnt_pools_are_inherited_when_densification_changes_the_number_of_gau
     down), and the old shape's entries go -- no first-frame read-back per densification.  Outside that window nothing is inherited."""
     from diff_gaussian_rasterization import _backend as B
     keep = (dict(B._capacity), dict(B._mask_need), dict(B._staged_need), dict(B._recent_P), dict(B._stats))
+    keep_sized = [dict(d) for d in B._sized_for]
     try:
-        for d in (B._capacity, B._mask_need, B._staged_need, B._recent_P):
+        for d in (B._capacity, B._mask_need, B._staged_need, B._recent_P) + tuple(B._sized_for):
             d.clear()
         k0 = ("cuda:0", 100_000, 800, 800)
         B._inherit_learnt(k0)                                   # first shape at this resolution: nothing to inherit
@@ -148,8 +149,59 @@ def test_learnt_pools_are_inherited_when_densification_changes_the_number_of_gau
         B._inherit_learnt(k4)
         assert k4 not in B._capacity
     finally:
-        for d, k in zip((B._capacity, B._mask_need, B._staged_need, B._recent_P, B._stats), keep):
+        for d, k in zip((B._capacity, B._mask_need, B._staged_need, B._recent_P, B._stats) + tuple(B._sized_for), list(keep) + keep_sized):
             d.clear(); d.update(k)
+
+
+def _walk_inherited_pools(seed_P, other_P, round_trips, res=(800, 800)):
+    """Seeds learnt values at seed_P, then alternates other_P / seed_P through _backend._inherit_learnt; returns the seeded triple and
+    the (capacity, mask need, staged need) triples found at every arrival at seed_P and at other_P.  All state is put back."""
+    from diff_gaussian_rasterization import _backend as B
+    dicts = (B._capacity, B._mask_need, B._staged_need, B._recent_P, B._stats) + tuple(B._sized_for)
+    keep = [dict(d) for d in dicts]
+    try:
+        for d in dicts:
+            if d is not B._stats:
+                d.clear()
+        ka, kb = ("cuda:0", seed_P, ) + res, ("cuda:0", other_P, ) + res
+        B._inherit_learnt(ka)                                   # the first frame at this resolution
+        seeded = (40 << 16, 12_345, 678_901)
+        B._capacity[ka], B._mask_need[ka], B._staged_need[ka] = seeded
+        at_seed, at_other = [], []
+        for _ in range(round_trips):
+            B._inherit_learnt(kb)
+            at_other.append((B._capacity[kb], B._mask_need[kb], B._staged_need[kb]))
+            assert ka not in B._capacity and ka not in B._mask_need and ka not in B._staged_need
+            B._inherit_learnt(ka)
+            at_seed.append((B._capacity[ka], B._mask_need[ka], B._staged_need[ka]))
+            assert len(B._capacity) == len(B._mask_need) == len(B._staged_need) == 1          # the dicts stay bounded
+        return seeded, at_seed, at_other
+    finally:
+        for d, k in zip(dicts, keep):
+            d.clear(); d.update(k)
+
+
+def test_inherited_pools_do_not_compound_over_prune_and_regrow_cycles():
+    """1.0 M -> 0.7 M -> 1.0 M ten times (densify up, prune after every opacity reset): a capacity already sized for 1.0 M does not
+    grow when the count returns to 1.0 M, so all three learnt values at the tenth arrival are those of the first -- and those are the
+    seeded ones, the count at 1.0 M never having changed.  Scaling by P/prev instead multiplied them by 1.43 per round trip (1.43^9 =
+    25x between the first and the tenth arrival).  The expected values follow from that rule; nothing here is a measurement."""
+    seeded, at_seed, at_other = _walk_inherited_pools(1_000_000, 700_000, 10)
+    assert at_seed[0] == seeded, (at_seed[0], seeded)
+    assert at_seed[9] == at_seed[0], (at_seed[9], at_seed[0])
+    assert all(v == seeded for v in at_other), at_other                       # pruned: inherited as it is
+
+
+def test_inherited_pools_do_not_compound_when_two_models_alternate():
+    """A viewer or an evaluation alternating two checkpoints at one resolution, P_A = 150 k and P_B = 100 k.  Seeded at the larger:
+    nothing ever grows.  Seeded at the smaller: the first arrival at 150 k scales by >= 1.5 (sized for 150 k from then on), every
+    later arrival at either model finds exactly those values."""
+    seeded, at_a, at_b = _walk_inherited_pools(150_000, 100_000, 10)
+    assert at_a[0] == seeded and at_a[9] == at_a[0] and all(v == seeded for v in at_b), (seeded, at_a, at_b)
+    seeded, at_b, at_a = _walk_inherited_pools(100_000, 150_000, 10)
+    assert all(a >= int(s * 1.5) for a, s in zip(at_a[0], seeded)) and at_a[0][0] % (1 << 16) == 0
+    assert all(a <= int(s * 1.5) + (1 << 16) for a, s in zip(at_a[0], seeded))          # scaled once by 1.5 (+ rounding), not more
+    assert at_a[9] == at_a[0] and at_b[9] == at_b[0] == at_a[0], (at_a, at_b)
 
 
 def test_per_call_modes_are_per_thread_and_nest():

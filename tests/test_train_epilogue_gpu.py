@@ -805,6 +805,7 @@ def test_densify_and_prune_on_the_device_equals_the_references_own_method():
     assert len(rows) == 5
     for x in rows:
         assert x["n_ref"] == x["n_ours"] and x["ret_ref"] == x["ret_ours"], x
+        assert x["next_normal_equal"] is True, x                                           # the generator stands where the reference leaves it
         assert x["ret_ref"][0] > 0 and x["ret_ref"][1] > 0 and x["ret_ref"][2] > 0, x      # clones, splits and prunes all occurred
         for k, v in x["diff"].items():
             assert v == 0.0, (k, v, x)
