@@ -5,6 +5,7 @@
 // buffer management (reference rasterize_points.cu:28-122).  No torch types, no global state,
 // every launch on the caller's stream.
 #include "gof_common.h"
+#include "radix.h"
 #include "gof_status.h"
 #include <algorithm>
 #include <atomic>
@@ -42,21 +43,6 @@ __global__ void sh_grad_expand(int P, int D, int M, int n_views, const float* me
                                long packed_stride, float scale, float* out_dc, long stride_dc, float* out_rest, long stride_rest);
 
 uint32_t higher_msb(uint32_t n);
-size_t scan_tmp_words(size_t n);
-hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
-                           const uint32_t** total_dev_out, hipStream_t stream);
-size_t rs_tmp_words(size_t n);
-const uint32_t* radix_sort_error_flag(const uint32_t* tmp, size_t n, int end_bit);
-hipError_t radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
-                                uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev = nullptr);
-hipError_t radix_sort_pairs_u32_z(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
-                                  uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev,
-                                  size_t zero_words_behind, bool first_hist_done, bool scratch_zeroed = false);
-size_t radix_zero_words(size_t n, int end_bit);
-uint32_t* radix_classic_hist(uint32_t* tmp, size_t n, int end_bit);
-uint32_t rs_block_items();
-uint32_t rs_units(size_t n);
-int radix_passes(int end_bit);
 uint32_t emit_instances_grid(uint32_t slots, int P);
 __global__ void emit_instances(int P, const uint32_t* order, const uint32_t* order_off, const uint32_t* minxy_sorted, const uint32_t* wh_sorted,
                                uint32_t* tiles, uint32_t* gids, uint32_t gx, uint32_t capacity, uint32_t* inst_first, uint32_t* hist0, uint32_t hist_stride);

@@ -10,7 +10,7 @@
 //     pass: one wave per slice of CLOUD_SLICE consecutive OUTPUT slots; a lane finds its triangle with a search into the scanned
 //     counts and its row by walking the rows -- in a wave whose lanes share one triangle (every wave inside a large triangle) the
 //     rows in front of the slice are skipped 64 at a time by the whole wave first.
-// (b) grid of cells (edge r (1 + 2^-20): see thin_cell), 3 x 21-bit key, two stable radix sorts (low / high word, as tsdf.hip), points
+// (b) grid of cells (edge r (1 + 2^-20): see thin_cell), 3 x 21-bit key, radix.h's sort_keys63, points
 //     gathered into key order; rounds over the undecided: a point looks at the lower-index points within r in its 27 cells (9 key
 //     ranges of 3 cells, one binary search each): a kept one removes it, none undecided keeps it.  States move undecided -> decided
 //     only, so a stale read is conservative and the result does not depend on the schedule.
@@ -25,29 +25,12 @@
 #include <cmath>
 #include "../../include/gof_hip.h"
 #include "../../include/gof_cloud_hip.h"
-#include "gof_common.h"
+#include "radix.h"
+#include "gof_geom.h"
 
 namespace gof {
 
-hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
-                           const uint32_t** total_dev_out, hipStream_t stream);
-size_t scan_tmp_words(size_t n);
-hipError_t radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
-                                uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev = nullptr);
-size_t rs_tmp_words(size_t n);
-
-typedef unsigned long long u64;
-
 constexpr uint32_t CLOUD_F_NONFINITE = 1u, CLOUD_F_INDEX = 2u, CLOUD_F_CELLS = 4u;
-
-__device__ __forceinline__ u64 ordered64(double d) { const u64 b = (u64)__double_as_longlong(d); return (b >> 63) ? ~b : (b | 0x8000000000000000ull); }
-__device__ __forceinline__ double unordered64(u64 u) { return __longlong_as_double((long long)((u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u)); }
-__device__ __forceinline__ bool finite3(double x, double y, double z) { return fabs(x) <= DBL_MAX && fabs(y) <= DBL_MAX && fabs(z) <= DBL_MAX; }
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += ((u64)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o) << 32 | (uint32_t)__shfl_xor((int)(uint32_t)v, o));
-    return v;
-}
 
 // header words shared by the three workspaces: u64 [0..2] min, [3..5] max (ordered encoding), [6] flags, [7..] counters
 constexpr int H_FLAGS = 6, H_CNT0 = 7, H_CNT1 = 8, H_CNT2 = 9, H_CNT3 = 10, HDR_WORDS = 16;
@@ -214,15 +197,13 @@ struct SampleWs { u64* hdr; uint32_t* counts; uint32_t* tmp; };
 static size_t sample_layout(int64_t NT, void* base, SampleWs* out)
 {
     const size_t n = (size_t)(NT < 0 ? 0 : NT) + 1;
-    size_t o = 0;
-    char* p = static_cast<char*>(base);
-    auto carve = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
+    Carver c{ static_cast<char*>(base), 0 };
     SampleWs w;
-    w.hdr = (u64*)carve(HDR_WORDS * 8);
-    w.counts = (uint32_t*)carve(n * 4);
-    w.tmp = (uint32_t*)carve(scan_tmp_words(n) * 4);
+    w.hdr = c.take<u64>(HDR_WORDS);
+    w.counts = c.take<uint32_t>(n);
+    w.tmp = c.take<uint32_t>(scan_tmp_words(n));
     if (out) *out = w;
-    return o + ALIGN;
+    return c.total();
 }
 
 // =====================================================================================================================================
@@ -265,12 +246,6 @@ thin_keys(int64_t N, const double* __restrict__ pts, double r, u64* __restrict__
     keys[i] = key;
     lo32[i] = (uint32_t)key;
     idx[i] = (uint32_t)i;
-}
-__global__ void __launch_bounds__(256)
-thin_keys_hi(int64_t N, const u64* __restrict__ keys, const uint32_t* __restrict__ idx, uint32_t* __restrict__ hi32)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < N) hi32[i] = (uint32_t)(keys[idx[i]] >> 32);
 }
 __global__ void __launch_bounds__(256)
 thin_gather(int64_t N, const double* __restrict__ pts, const u64* __restrict__ keys, const uint32_t* __restrict__ idx,
@@ -343,25 +318,23 @@ thin_finish(int64_t N, const uint32_t* __restrict__ sorder, const uint32_t* __re
     if ((threadIdx.x & 63) == 0 && k) atomicAdd(&hdr[H_CNT0], k);
 }
 
-struct ThinWs { u64* hdr; uint32_t* cnt; u64* keys; u64* skeys; double* spts; uint32_t* sorder; uint32_t* state; uint32_t* k[2]; uint32_t* v[2]; uint32_t* hi[2]; uint32_t* tmp; };
+struct ThinWs { u64* hdr; uint32_t* cnt; u64* keys; u64* skeys; double* spts; uint32_t* sorder; uint32_t* state; Sort63Ws s; };
 static size_t thin_layout(int64_t N, void* base, ThinWs* out)
 {
     const size_t n = (size_t)(N < 1 ? 1 : N);
-    size_t o = 0;
-    char* p = static_cast<char*>(base);
-    auto carve = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
+    Carver c{ static_cast<char*>(base), 0 };
     ThinWs w;
-    w.hdr = (u64*)carve(HDR_WORDS * 8);
-    w.cnt = (uint32_t*)carve((THIN_BATCH_MAX + 2) * 4);
-    w.keys = (u64*)carve(n * 8);
-    w.skeys = (u64*)carve(n * 8);
-    w.spts = (double*)carve(n * 24);
-    w.sorder = (uint32_t*)carve(n * 4);
-    w.state = (uint32_t*)carve(n * 4);
-    for (int i = 0; i < 2; i++) { w.k[i] = (uint32_t*)carve(n * 4); w.v[i] = (uint32_t*)carve(n * 4); w.hi[i] = (uint32_t*)carve(n * 4); }
-    w.tmp = (uint32_t*)carve(rs_tmp_words(n) * 4);
+    w.hdr = c.take<u64>(HDR_WORDS);
+    w.cnt = c.take<uint32_t>(THIN_BATCH_MAX + 2);
+    w.keys = c.take<u64>(n);
+    w.skeys = c.take<u64>(n);
+    w.spts = c.take<double>(3 * n);
+    w.sorder = c.take<uint32_t>(n);
+    w.state = c.take<uint32_t>(n);
+    sort63_carve(c, n, w.s);
+    w.s.tmp = c.take<uint32_t>(rs_tmp_words(n));
     if (out) *out = w;
-    return o + ALIGN;
+    return c.total();
 }
 
 // =====================================================================================================================================
@@ -539,40 +512,31 @@ static size_t nn_index_layout(int64_t NS, void* base, NnIndex* out)
 {
     const size_t n = (size_t)(NS < 1 ? 1 : NS);
     const size_t nb = (n + NN_BOX - 1) / NN_BOX, ng = (nb + NN_GROUP - 1) / NN_GROUP;
-    size_t o = 0;
-    char* p = static_cast<char*>(base);
-    auto carve = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
+    Carver c{ static_cast<char*>(base), 0 };
     NnIndex w;
-    w.hdr = (u64*)carve(HDR_WORDS * 8);
-    w.sorted = (double*)carve(n * 24);
-    w.sidx = (uint32_t*)carve(n * 4);
-    w.scodes = (uint32_t*)carve(n * 4);
-    w.boxes = (NnBox*)carve(nb * sizeof(NnBox));
-    w.groups = (NnBox*)carve(ng * sizeof(NnBox));
-    w.ka = (uint32_t*)carve(n * 4); w.kb = (uint32_t*)carve(n * 4); w.va = (uint32_t*)carve(n * 4); w.vb = (uint32_t*)carve(n * 4);
-    w.tmp = (uint32_t*)carve(rs_tmp_words(n) * 4);
+    w.hdr = c.take<u64>(HDR_WORDS);
+    w.sorted = c.take<double>(3 * n);
+    w.sidx = c.take<uint32_t>(n);
+    w.scodes = c.take<uint32_t>(n);
+    w.boxes = c.take<NnBox>(nb);
+    w.groups = c.take<NnBox>(ng);
+    w.ka = c.take<uint32_t>(n); w.kb = c.take<uint32_t>(n); w.va = c.take<uint32_t>(n); w.vb = c.take<uint32_t>(n);
+    w.tmp = c.take<uint32_t>(rs_tmp_words(n));
     if (out) *out = w;
-    return o + ALIGN;
+    return c.total();
 }
 struct NnQueryWs { u64* hdr; uint32_t *ka, *kb, *va, *vb, *tmp; };
 static size_t nn_query_layout(int64_t NQ, void* base, NnQueryWs* out)
 {
     const size_t n = (size_t)(NQ < 1 ? 1 : NQ);
-    size_t o = 0;
-    char* p = static_cast<char*>(base);
-    auto carve = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
+    Carver c{ static_cast<char*>(base), 0 };
     NnQueryWs w;
-    w.hdr = (u64*)carve(HDR_WORDS * 8);
-    w.ka = (uint32_t*)carve(n * 4); w.kb = (uint32_t*)carve(n * 4); w.va = (uint32_t*)carve(n * 4); w.vb = (uint32_t*)carve(n * 4);
-    w.tmp = (uint32_t*)carve(rs_tmp_words(n) * 4);
+    w.hdr = c.take<u64>(HDR_WORDS);
+    w.ka = c.take<uint32_t>(n); w.kb = c.take<uint32_t>(n); w.va = c.take<uint32_t>(n); w.vb = c.take<uint32_t>(n);
+    w.tmp = c.take<uint32_t>(rs_tmp_words(n));
     if (out) *out = w;
-    return o + ALIGN;
+    return c.total();
 }
-
-static inline dim3 cloud_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
-static inline void* ws_aligned(void* ws) { return reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(ws))); }
-static inline const void* ws_aligned(const void* ws) { return reinterpret_cast<const void*>(align_up(reinterpret_cast<size_t>(ws))); }
-static bool bad_count(int64_t n) { return n < 0 || n >= ((int64_t)1 << 31); }
 
 static int flags_error(u64 flags, const char* who)
 {
@@ -605,7 +569,7 @@ int gof_cloud_sample_count(int64_t NV, const double* V, int64_t NT, const int32_
     GOF_PROFILE("cloud_sample_count", stream);
     hipLaunchKernelGGL(cloud_init_hdr, dim3(1), dim3(64), 0, stream, w.hdr);
     const int64_t n = (NT + 1 > NV ? NT + 1 : NV);
-    hipLaunchKernelGGL(cloud_sample_count, cloud_grid(n), dim3(256), 0, stream, NV, V, NT, T, thresh, w.counts, w.hdr);
+    hipLaunchKernelGGL(cloud_sample_count, grid_of(n), dim3(256), 0, stream, NV, V, NT, T, thresh, w.counts, w.hdr);
     GOF_LAUNCH_CHECK(stream, 0);
     GOF_HIP_CHECK(device_scan_u32(w.counts, nullptr, w.counts, (size_t)NT + 1, false, w.tmp, nullptr, stream));
     u64 h[2];
@@ -653,25 +617,21 @@ int gof_cloud_thin(int64_t N, const double* points, double r, uint8_t* keep, voi
     if (!points || !keep) { set_error("cloud_thin: points / keep is NULL"); return GOF_E_INVALID; }
     GOF_PROFILE("cloud_thin", stream);
     hipLaunchKernelGGL(cloud_bbox, dim3((unsigned)min((int64_t)2048, (N + 255) / 256)), dim3(256), 0, stream, N, points, w.hdr);
-    hipLaunchKernelGGL(thin_keys, cloud_grid(N), dim3(256), 0, stream, N, points, r, w.hdr, w.keys, w.k[0], w.v[0]);
+    hipLaunchKernelGGL(thin_keys, grid_of(N), dim3(256), 0, stream, N, points, r, w.hdr, w.keys, w.s.lo[0], w.s.idx[0]);
     GOF_LAUNCH_CHECK(stream, 0);
-    uint32_t *k1 = nullptr, *v1 = nullptr, *k2 = nullptr, *v2 = nullptr;
-    GOF_HIP_CHECK(radix_sort_pairs_u32(w.k[0], w.v[0], w.k[1], w.v[1], (size_t)N, 32, w.tmp, &k1, &v1, stream, nullptr));
-    hipLaunchKernelGGL(thin_keys_hi, cloud_grid(N), dim3(256), 0, stream, N, w.keys, v1, w.hi[0]);
-    GOF_LAUNCH_CHECK(stream, 0);
-    uint32_t* v_other = v1 == w.v[0] ? w.v[1] : w.v[0];
-    GOF_HIP_CHECK(radix_sort_pairs_u32(w.hi[0], v1, w.hi[1], v_other, (size_t)N, 31, w.tmp, &k2, &v2, stream, nullptr));
-    hipLaunchKernelGGL(thin_gather, cloud_grid(N), dim3(256), 0, stream, N, points, w.keys, v2, w.skeys, w.spts, w.sorder, w.state);
+    uint32_t* order = nullptr;
+    GOF_HIP_CHECK(sort_keys63(w.keys, (size_t)N, w.s, &order, stream));
+    hipLaunchKernelGGL(thin_gather, grid_of(N), dim3(256), 0, stream, N, points, w.keys, order, w.skeys, w.spts, w.sorder, w.state);
     GOF_LAUNCH_CHECK(stream, 0);
     // the sort's buffers are dead now: the two lists of the undecided live in its key buffers
-    uint32_t* lists[2] = { w.k[0], w.k[1] };
+    uint32_t* lists[2] = { w.s.lo[0], w.s.lo[1] };
     const double r2 = r * r;
     int64_t count = N, rounds = 0, readbacks = 0;
     int batch = 4;
     while (count > 0) {
         GOF_HIP_CHECK(hipMemsetAsync(w.cnt + 1, 0, (size_t)batch * sizeof(uint32_t), stream));
         for (int b = 0; b < batch; b++, rounds++) {
-            hipLaunchKernelGGL(thin_round, cloud_grid(count), dim3(256), 0, stream, N, rounds == 0 ? (const uint32_t*)nullptr : lists[rounds & 1],
+            hipLaunchKernelGGL(thin_round, grid_of(count), dim3(256), 0, stream, N, rounds == 0 ? (const uint32_t*)nullptr : lists[rounds & 1],
                                w.cnt + b, w.skeys, w.spts, w.sorder, w.state, lists[(rounds + 1) & 1], w.cnt + b + 1, r2, w.hdr);
         }
         GOF_LAUNCH_CHECK(stream, 0);
@@ -687,7 +647,7 @@ int gof_cloud_thin(int64_t N, const double* points, double r, uint8_t* keep, voi
         hipLaunchKernelGGL(cloud_set_u32, dim3(1), dim3(64), 0, stream, w.cnt, left);
         if (batch < THIN_BATCH_MAX) batch *= 2;
     }
-    hipLaunchKernelGGL(thin_finish, cloud_grid(N), dim3(256), 0, stream, N, w.sorder, w.state, keep, w.hdr);
+    hipLaunchKernelGGL(thin_finish, grid_of(N), dim3(256), 0, stream, N, w.sorder, w.state, keep, w.hdr);
     hipLaunchKernelGGL(cloud_set_words, dim3(1), dim3(64), 0, stream, w.hdr + 11, (u64)rounds, (u64)readbacks);
     GOF_LAUNCH_CHECK(stream, 0);
     u64 kept = 0;
@@ -726,7 +686,7 @@ int gof_cloud_nn_build(int64_t NS, const double* ref, void* index, size_t index_
     GOF_PROFILE("cloud_nn_build", stream);
     const int64_t nb = (NS + NN_BOX - 1) / NN_BOX, ng = (nb + NN_GROUP - 1) / NN_GROUP;
     hipLaunchKernelGGL(cloud_bbox, dim3((unsigned)min((int64_t)2048, (NS + 255) / 256)), dim3(256), 0, stream, NS, ref, w.hdr);
-    hipLaunchKernelGGL(nn_morton, cloud_grid(NS), dim3(256), 0, stream, NS, ref, w.hdr, w.ka, w.va, w.hdr);
+    hipLaunchKernelGGL(nn_morton, grid_of(NS), dim3(256), 0, stream, NS, ref, w.hdr, w.ka, w.va, w.hdr);
     GOF_LAUNCH_CHECK(stream, 0);
     uint32_t *kr = nullptr, *vr = nullptr;
     GOF_HIP_CHECK(radix_sort_pairs_u32(w.ka, w.va, w.kb, w.vb, (size_t)NS, 30, w.tmp, &kr, &vr, stream));
@@ -757,12 +717,12 @@ int gof_cloud_nn_query(int64_t NS, const void* index, size_t index_bytes, int64_
     GOF_PROFILE("cloud_nn_query", stream);
     hipLaunchKernelGGL(cloud_set_words, dim3(1), dim3(64), 0, stream, w.hdr + 11, (u64)NQ, (u64)NS);
     if (NS == 0) {
-        hipLaunchKernelGGL(nn_fill_empty, cloud_grid(NQ), dim3(256), 0, stream, NQ, dist, nearest);
+        hipLaunchKernelGGL(nn_fill_empty, grid_of(NQ), dim3(256), 0, stream, NQ, dist, nearest);
         GOF_LAUNCH_CHECK(stream, 0);
         return GOF_OK;
     }
     const int64_t nb = (NS + NN_BOX - 1) / NN_BOX, ng = (nb + NN_GROUP - 1) / NN_GROUP;
-    hipLaunchKernelGGL(nn_morton, cloud_grid(NQ), dim3(256), 0, stream, NQ, query, x.hdr, w.ka, w.va, w.hdr);
+    hipLaunchKernelGGL(nn_morton, grid_of(NQ), dim3(256), 0, stream, NQ, query, x.hdr, w.ka, w.va, w.hdr);
     GOF_LAUNCH_CHECK(stream, 0);
     uint32_t *kr = nullptr, *vr = nullptr;
     GOF_HIP_CHECK(radix_sort_pairs_u32(w.ka, w.va, w.kb, w.vb, (size_t)NQ, 30, w.tmp, &kr, &vr, stream));

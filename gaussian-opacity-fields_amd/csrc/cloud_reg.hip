@@ -9,7 +9,7 @@
 // (a) one lane per point, the polygon's (u, v) pairs in LDS (16 B per vertex, dynamic: K <= 4096 = 64 KB); pass 1 writes a keep flag,
 //     the library's scan turns the flags into output rows, pass 2 evaluates the transformation again (12 multiplications: cheaper
 //     than keeping 24 B per point) and writes the kept points in input order.
-// (b) 3 x 21-bit cell key, two stable radix sorts (low / high word, as gof_cloud_thin), so that a voxel's points are consecutive and
+// (b) 3 x 21-bit cell key, radix.h's sort_keys63, so that a voxel's points are consecutive and
 //     in input order; the first point of every voxel is flagged, the scan numbers the voxels in ascending key order, and the lane
 //     of a first point adds its voxel's points one after the other (serial by contract: the sum has ONE order).
 // (c) a sum = the balanced binary tree over the source points in index order: xor butterfly inside a wave (both lanes of a pair
@@ -21,35 +21,18 @@
 #include <cmath>
 #include "../../include/gof_hip.h"
 #include "../../include/gof_cloud_reg_hip.h"
-#include "gof_common.h"
+#include "radix.h"
+#include "gof_geom.h"
 
 namespace gof {
 
-hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
-                           const uint32_t** total_dev_out, hipStream_t stream);
-size_t scan_tmp_words(size_t n);
-hipError_t radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
-                                uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev = nullptr);
-size_t rs_tmp_words(size_t n);
-
 namespace reg {
-
-typedef unsigned long long u64;
 
 constexpr uint32_t F_NONFINITE = 1u, F_INDEX = 2u, F_CELLS = 4u;
 // header words of every workspace: u64 [0..2] per-axis minimum (ordered encoding), [3] flags, [4] a count
 constexpr int H_FLAGS = 3, H_COUNT = 4, HDR_WORDS = 8;
 constexpr int MAX_POLYGON = 4096;
 constexpr int64_t VOX_MAXC = (1 << 21) - 1;
-
-__device__ __forceinline__ u64 ordered64(double d) { const u64 b = (u64)__double_as_longlong(d); return (b >> 63) ? ~b : (b | 0x8000000000000000ull); }
-__device__ __forceinline__ double unordered64(u64 u) { return __longlong_as_double((long long)((u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u)); }
-__device__ __forceinline__ bool finite3(double x, double y, double z) { return fabs(x) <= DBL_MAX && fabs(y) <= DBL_MAX && fabs(z) <= DBL_MAX; }
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += ((u64)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o) << 32 | (uint32_t)__shfl_xor((int)(uint32_t)v, o));
-    return v;
-}
 
 __global__ void reg_init_hdr(u64* hdr)
 {
@@ -131,15 +114,13 @@ struct CropWs { u64* hdr; uint32_t* flags; uint32_t* tmp; };
 static size_t crop_layout(int64_t N, void* base, CropWs* out)
 {
     const size_t n = (size_t)(N < 0 ? 0 : N) + 1;
-    size_t o = 0;
-    char* p = static_cast<char*>(base);
-    auto carve = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
+    Carver c{ static_cast<char*>(base), 0 };
     CropWs w;
-    w.hdr = (u64*)carve(HDR_WORDS * 8);
-    w.flags = (uint32_t*)carve(n * 4);
-    w.tmp = (uint32_t*)carve(scan_tmp_words(n) * 4);
+    w.hdr = c.take<u64>(HDR_WORDS);
+    w.flags = c.take<uint32_t>(n);
+    w.tmp = c.take<uint32_t>(scan_tmp_words(n));
     if (out) *out = w;
-    return o + ALIGN;
+    return c.total();
 }
 
 // =====================================================================================================================================
@@ -188,12 +169,6 @@ reg_vox_keys(int64_t N, const double* __restrict__ pts, double v, u64* __restric
     lo32[i] = (uint32_t)key;
     idx[i] = (uint32_t)i;
 }
-__global__ void __launch_bounds__(256)
-reg_vox_keys_hi(int64_t N, const u64* __restrict__ keys, const uint32_t* __restrict__ idx, uint32_t* __restrict__ hi32)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < N) hi32[i] = (uint32_t)(keys[idx[i]] >> 32);
-}
 // heads[s] = 1 iff the s-th point in key order is the first of its voxel; heads[N] = 0
 __global__ void __launch_bounds__(256)
 reg_vox_heads(int64_t N, const u64* __restrict__ keys, const uint32_t* __restrict__ order, uint32_t* __restrict__ heads)
@@ -225,22 +200,20 @@ reg_vox_reduce(int64_t N, const double* __restrict__ pts, const uint32_t* __rest
     out_counts[me] = (int32_t)(q - s);
 }
 
-struct VoxWs { u64* hdr; u64* keys; uint32_t* heads; uint32_t* k[2]; uint32_t* v[2]; uint32_t* hi[2]; uint32_t* tmp; };
+struct VoxWs { u64* hdr; u64* keys; uint32_t* heads; Sort63Ws s; };      // (s.tmp serves the scan of the heads as well)
 static size_t vox_layout(int64_t N, void* base, VoxWs* out)
 {
     const size_t n = (size_t)(N < 1 ? 1 : N);
-    size_t o = 0;
-    char* p = static_cast<char*>(base);
-    auto carve = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
+    Carver c{ static_cast<char*>(base), 0 };
     VoxWs w;
-    w.hdr = (u64*)carve(HDR_WORDS * 8);
-    w.keys = (u64*)carve(n * 8);
-    w.heads = (uint32_t*)carve((n + 1) * 4);
-    for (int i = 0; i < 2; i++) { w.k[i] = (uint32_t*)carve(n * 4); w.v[i] = (uint32_t*)carve(n * 4); w.hi[i] = (uint32_t*)carve(n * 4); }
+    w.hdr = c.take<u64>(HDR_WORDS);
+    w.keys = c.take<u64>(n);
+    w.heads = c.take<uint32_t>(n + 1);
     const size_t t1 = rs_tmp_words(n), t2 = scan_tmp_words(n + 1);
-    w.tmp = (uint32_t*)carve((t1 > t2 ? t1 : t2) * 4);
+    sort63_carve(c, n, w.s);
+    w.s.tmp = c.take<uint32_t>(t1 > t2 ? t1 : t2);
     if (out) *out = w;
-    return o + ALIGN;
+    return c.total();
 }
 
 // =====================================================================================================================================
@@ -347,20 +320,14 @@ static size_t sums_layout(int64_t N, void* base, SumsWs* out)
 {
     const size_t n = (size_t)(N < 1 ? 1 : N);
     const size_t m1 = (n + 255) / 256, m2 = (m1 + 255) / 256;
-    size_t o = 0;
-    char* p = static_cast<char*>(base);
-    auto carve = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
+    Carver c{ static_cast<char*>(base), 0 };
     SumsWs w;
-    w.hdr = (u64*)carve(HDR_WORDS * 8);
-    w.a = (double*)carve(SUMS_MAX_C * m1 * 8);
-    w.b = (double*)carve(SUMS_MAX_C * m2 * 8);
+    w.hdr = c.take<u64>(HDR_WORDS);
+    w.a = c.take<double>(SUMS_MAX_C * m1);
+    w.b = c.take<double>(SUMS_MAX_C * m2);
     if (out) *out = w;
-    return o + ALIGN;
+    return c.total();
 }
-
-static inline dim3 reg_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
-static inline void* ws_aligned(void* ws) { return reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(ws))); }
-static bool bad_count(int64_t n) { return n < 0 || n >= ((int64_t)1 << 31); }
 
 static int flags_error(u64 flags, const char* who)
 {
@@ -437,7 +404,7 @@ int gof_cloud_transform(int64_t N, const double* points, const double* matrix, d
     GOF_PROFILE("cloud_transform", stream);
     u64* hdr = static_cast<u64*>(ws_aligned(ws));
     hipLaunchKernelGGL(reg_init_hdr, dim3(1), dim3(64), 0, stream, hdr);
-    hipLaunchKernelGGL(reg_transform, reg_grid(N), dim3(256), 0, stream, N, points, M, out, hdr);
+    hipLaunchKernelGGL(reg_transform, grid_of(N), dim3(256), 0, stream, N, points, M, out, hdr);
     GOF_LAUNCH_CHECK(stream, 0);
     u64 flags = 0;
     GOF_HIP_CHECK(hipMemcpyAsync(&flags, hdr + H_FLAGS, 8, hipMemcpyDeviceToHost, stream));
@@ -468,11 +435,11 @@ int gof_cloud_crop(int64_t N, const double* points, const double* matrix, int ax
     crop_layout(N, ws_aligned(ws), &w);
     GOF_PROFILE("cloud_crop", stream);
     hipLaunchKernelGGL(reg_init_hdr, dim3(1), dim3(64), 0, stream, w.hdr);
-    hipLaunchKernelGGL(reg_crop_flags, reg_grid(N + 1), dim3(256), (size_t)(K > 0 ? K : 1) * 16, stream, N, points, M, axis, axis_min, axis_max, (int)K,
+    hipLaunchKernelGGL(reg_crop_flags, grid_of(N + 1), dim3(256), (size_t)(K > 0 ? K : 1) * 16, stream, N, points, M, axis, axis_min, axis_max, (int)K,
                        polygon, w.flags, w.hdr);
     GOF_LAUNCH_CHECK(stream, 0);
     GOF_HIP_CHECK(device_scan_u32(w.flags, nullptr, w.flags, (size_t)N + 1, false, w.tmp, nullptr, stream));
-    hipLaunchKernelGGL(reg_crop_emit, reg_grid(N), dim3(256), 0, stream, N, points, M, w.flags, out_points, out_index);
+    hipLaunchKernelGGL(reg_crop_emit, grid_of(N), dim3(256), 0, stream, N, points, M, w.flags, out_points, out_index);
     GOF_LAUNCH_CHECK(stream, 0);
     u64 flags = 0;
     uint32_t kept = 0;
@@ -503,17 +470,13 @@ int gof_cloud_voxel(int64_t N, const double* points, double voxel, double* out_p
     GOF_PROFILE("cloud_voxel", stream);
     hipLaunchKernelGGL(reg_init_hdr, dim3(1), dim3(64), 0, stream, w.hdr);
     hipLaunchKernelGGL(reg_min, dim3((unsigned)min((int64_t)2048, (N + 255) / 256)), dim3(256), 0, stream, N, points, w.hdr);
-    hipLaunchKernelGGL(reg_vox_keys, reg_grid(N), dim3(256), 0, stream, N, points, voxel, w.hdr, w.keys, w.k[0], w.v[0]);
+    hipLaunchKernelGGL(reg_vox_keys, grid_of(N), dim3(256), 0, stream, N, points, voxel, w.hdr, w.keys, w.s.lo[0], w.s.idx[0]);
     GOF_LAUNCH_CHECK(stream, 0);
-    uint32_t *k1 = nullptr, *v1 = nullptr, *k2 = nullptr, *v2 = nullptr;
-    GOF_HIP_CHECK(radix_sort_pairs_u32(w.k[0], w.v[0], w.k[1], w.v[1], (size_t)N, 32, w.tmp, &k1, &v1, stream, nullptr));
-    hipLaunchKernelGGL(reg_vox_keys_hi, reg_grid(N), dim3(256), 0, stream, N, w.keys, v1, w.hi[0]);
+    uint32_t* order = nullptr;
+    GOF_HIP_CHECK(sort_keys63(w.keys, (size_t)N, w.s, &order, stream));
+    hipLaunchKernelGGL(reg_vox_heads, grid_of(N + 1), dim3(256), 0, stream, N, w.keys, order, w.heads);
     GOF_LAUNCH_CHECK(stream, 0);
-    uint32_t* v_other = v1 == w.v[0] ? w.v[1] : w.v[0];
-    GOF_HIP_CHECK(radix_sort_pairs_u32(w.hi[0], v1, w.hi[1], v_other, (size_t)N, 31, w.tmp, &k2, &v2, stream, nullptr));
-    hipLaunchKernelGGL(reg_vox_heads, reg_grid(N + 1), dim3(256), 0, stream, N, w.keys, v2, w.heads);
-    GOF_LAUNCH_CHECK(stream, 0);
-    GOF_HIP_CHECK(device_scan_u32(w.heads, nullptr, w.heads, (size_t)N + 1, false, w.tmp, nullptr, stream));
+    GOF_HIP_CHECK(device_scan_u32(w.heads, nullptr, w.heads, (size_t)N + 1, false, w.s.tmp, nullptr, stream));
     // the flags first: a non-finite point has no cell, and nothing is written for a cloud that is refused
     u64 flags = 0;
     uint32_t nv = 0;
@@ -521,7 +484,7 @@ int gof_cloud_voxel(int64_t N, const double* points, double voxel, double* out_p
     GOF_HIP_CHECK(hipMemcpyAsync(&nv, w.heads + N, 4, hipMemcpyDeviceToHost, stream));
     GOF_HIP_CHECK(hipStreamSynchronize(stream));
     if (int e = flags_error(flags, "cloud_voxel")) return e;
-    hipLaunchKernelGGL(reg_vox_reduce, reg_grid(N), dim3(256), 0, stream, N, points, v2, w.heads, out_points, out_counts);
+    hipLaunchKernelGGL(reg_vox_reduce, grid_of(N), dim3(256), 0, stream, N, points, order, w.heads, out_points, out_counts);
     GOF_LAUNCH_CHECK(stream, 0);
     *num_voxels = (int64_t)nv;
     return GOF_OK;

@@ -17,17 +17,11 @@
 #include <algorithm>
 #include <cstring>
 #include "gof_common.h"
+#include "radix.h"
 #include "delaunay_predicates.h"
 #include "../../include/gof_delaunay_hip.h"
 
 namespace gof {
-
-size_t scan_tmp_words(size_t n);
-hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
-                           const uint32_t** total_dev_out, hipStream_t stream);
-size_t rs_tmp_words(size_t n);
-hipError_t radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
-                                uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev);
 
 using dt::Pred;
 

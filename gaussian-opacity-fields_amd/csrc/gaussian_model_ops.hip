@@ -15,11 +15,9 @@
 #include "../../include/gof_hip.h"
 #include "../../include/gof_train_hip.h"
 #include "gof_common.h"
+#include "radix.h"
 
 namespace gof {
-size_t scan_tmp_words(size_t n);                 // radix.hip
-hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
-                           const uint32_t** total_dev_out, hipStream_t stream);
 
 constexpr int F3_CHUNK = 128;
 

@@ -18,15 +18,13 @@
 #include "../../include/gof_hip.h"
 #include "../../include/gof_knn_hip.h"
 #include "gof_common.h"
+#include "radix.h"
+#include "gof_geom.h"
 
 namespace gof {
 
 constexpr int KNN_BOX = 256;
 constexpr int KNN_GROUP = 32;     // boxes per group
-
-hipError_t radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
-                                uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev = nullptr);
-size_t rs_tmp_words(size_t n);
 
 struct KnnBox { float lo[3]; float hi[3]; float pad[2]; };
 
@@ -189,21 +187,18 @@ knn_search(int64_t N, const float4* __restrict__ sorted, const uint32_t* __restr
 struct KnnWs { uint32_t* mm; uint32_t *ka, *kb, *va, *vb, *tmp; float4* sorted; KnnBox* boxes; KnnBox* groups; };
 static size_t knn_layout(int64_t N, void* base, KnnWs* out)
 {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t n = (size_t)(N < 1 ? 1 : N);
     const size_t nb = (n + KNN_BOX - 1) / KNN_BOX, ng = (nb + KNN_GROUP - 1) / KNN_GROUP;
-    size_t off = 0;
-    char* p = static_cast<char*>(base);
+    Carver c{ static_cast<char*>(base), 0 };
     KnnWs w;
-    auto carve = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += up(bytes); return r; };
-    w.mm = (uint32_t*)carve(8 * 4);
-    w.ka = (uint32_t*)carve(n * 4); w.kb = (uint32_t*)carve(n * 4); w.va = (uint32_t*)carve(n * 4); w.vb = (uint32_t*)carve(n * 4);
-    w.tmp = (uint32_t*)carve(rs_tmp_words(n) * 4);
-    w.sorted = (float4*)carve(n * 16);
-    w.boxes = (KnnBox*)carve(nb * sizeof(KnnBox));
-    w.groups = (KnnBox*)carve(ng * sizeof(KnnBox));
+    w.mm = c.take<uint32_t>(8);
+    w.ka = c.take<uint32_t>(n); w.kb = c.take<uint32_t>(n); w.va = c.take<uint32_t>(n); w.vb = c.take<uint32_t>(n);
+    w.tmp = c.take<uint32_t>(rs_tmp_words(n));
+    w.sorted = c.take<float4>(n);
+    w.boxes = c.take<KnnBox>(nb);
+    w.groups = c.take<KnnBox>(ng);
     if (out) *out = w;
-    return off + 256;
+    return c.total();
 }
 
 __global__ void knn_init_mm(uint32_t* mm)
@@ -227,7 +222,7 @@ int gof_knn_mean_dist3(int64_t N, const float* points, float* mean_dists, void* 
     if (!points || !mean_dists || !ws) { set_error("points / mean_dists / workspace is NULL"); return GOF_E_INVALID; }
     if (ws_bytes < gof_knn_ws_bytes(N)) { set_error("knn workspace too small"); return GOF_E_WORKSPACE; }
     KnnWs w;
-    knn_layout(N, reinterpret_cast<void*>((reinterpret_cast<size_t>(ws) + 255) & ~(size_t)255), &w);
+    knn_layout(N, ws_aligned(ws), &w);
     const int64_t nb = (N + KNN_BOX - 1) / KNN_BOX, ng = (nb + KNN_GROUP - 1) / KNN_GROUP;
     GOF_PROFILE("knn_mean_dist3", stream);
     hipLaunchKernelGGL(knn_init_mm, dim3(1), dim3(64), 0, stream, w.mm);

@@ -18,16 +18,12 @@
 #include "../../include/gof_hip.h"
 #include "../../include/gof_mesh_hip.h"
 #include "gof_common.h"
+#include "radix.h"
+#include "gof_geom.h"
 
 namespace gof {
 
-hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
-                           const uint32_t** total_dev_out, hipStream_t stream);
-size_t scan_tmp_words(size_t n);
-
 namespace mesh {
-
-typedef unsigned long long u64;
 
 constexpr int DIL_ROWS = 16, DIL_WORDS = 16;                          // the output tile
 constexpr int DIL_LDS_ROWS = DIL_ROWS + 2 * GOF_MESH_MAX_RADIUS;      // 78
@@ -35,9 +31,9 @@ constexpr int DIL_LDS_WORDS = DIL_WORDS + 2;                          // 18
 constexpr uint32_t F_RECORD = 1u, F_INDEX = 2u;
 constexpr int HDR_WORDS = 8;                                          // u32: [0] flags
 
-static inline void* ws_aligned(void* ws) { return reinterpret_cast<void*>((reinterpret_cast<size_t>(ws) + ALIGN - 1) & ~(ALIGN - 1)); }
-static inline bool bad_count(int64_t n) { return n < 0 || n >= ((int64_t)1 << 31) - 1; }
-static inline dim3 grid_of(int64_t n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
+// one less than the other units take (they accept N = 2^31 - 1): the compaction scans and launches over N + 1 flags, and this unit
+// keeps that count below 2^31 as well
+constexpr int64_t MESH_MAX_COUNT = ((int64_t)1 << 31) - 1;
 
 __global__ void mesh_init_hdr(uint32_t* hdr)
 {
@@ -181,17 +177,15 @@ struct CompactWs { uint32_t* hdr; uint32_t* vflags; uint32_t* fflags; uint32_t* 
 static size_t compact_layout(int64_t NV, int64_t NF, void* base, CompactWs* out)
 {
     const size_t nv = (size_t)(NV < 0 ? 0 : NV) + 1, nf = (size_t)(NF < 0 ? 0 : NF) + 1;
-    size_t o = 0;
-    char* p = static_cast<char*>(base);
-    auto carve = [&](size_t bytes) { char* r = p ? p + o : nullptr; o += align_up(bytes); return r; };
+    Carver c{ static_cast<char*>(base), 0 };
     CompactWs w;
-    w.hdr = (uint32_t*)carve(HDR_WORDS * 4);
-    w.vflags = (uint32_t*)carve(nv * 4);
-    w.fflags = (uint32_t*)carve(nf * 4);
+    w.hdr = c.take<uint32_t>(HDR_WORDS);
+    w.vflags = c.take<uint32_t>(nv);
+    w.fflags = c.take<uint32_t>(nf);
     const size_t t1 = scan_tmp_words(nv), t2 = scan_tmp_words(nf);
-    w.tmp = (uint32_t*)carve((t1 > t2 ? t1 : t2) * 4);
+    w.tmp = c.take<uint32_t>(t1 > t2 ? t1 : t2);
     if (out) *out = w;
-    return o + ALIGN;
+    return c.total();
 }
 
 } // namespace mesh
@@ -226,7 +220,7 @@ int gof_mesh_cull(int64_t NV, const float* vertices, int32_t num_views, const Go
                   uint8_t* keep, void* ws, size_t ws_bytes, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (bad_count(NV)) { set_error("mesh_cull: bad number of vertices (%lld)", (long long)NV); return GOF_E_INVALID; }
+    if (bad_count(NV, MESH_MAX_COUNT)) { set_error("mesh_cull: bad number of vertices (%lld)", (long long)NV); return GOF_E_INVALID; }
     if (num_views < 0 || mask_words < 0) { set_error("mesh_cull: bad number of views (%d) / mask words (%lld)", num_views, (long long)mask_words); return GOF_E_INVALID; }
     if (!ws) { set_error("mesh_cull: workspace is NULL"); return GOF_E_INVALID; }
     if (ws_bytes < gof_mesh_cull_ws_bytes(NV)) { set_error("mesh_cull: workspace too small"); return GOF_E_WORKSPACE; }
@@ -253,7 +247,7 @@ int gof_mesh_compact(int64_t NV, const uint8_t* keep, int64_t NF, const int32_t*
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!counts) { set_error("mesh_compact: counts is NULL"); return GOF_E_INVALID; }
     counts[0] = counts[1] = 0;
-    if (bad_count(NV) || bad_count(NF)) { set_error("mesh_compact: bad counts (%lld vertices, %lld faces)", (long long)NV, (long long)NF); return GOF_E_INVALID; }
+    if (bad_count(NV, MESH_MAX_COUNT) || bad_count(NF, MESH_MAX_COUNT)) { set_error("mesh_compact: bad counts (%lld vertices, %lld faces)", (long long)NV, (long long)NF); return GOF_E_INVALID; }
     if (!ws) { set_error("mesh_compact: workspace is NULL"); return GOF_E_INVALID; }
     if (ws_bytes < gof_mesh_compact_ws_bytes(NV, NF)) { set_error("mesh_compact: workspace too small"); return GOF_E_WORKSPACE; }
     if (NV && (!keep || !out_rows)) { set_error("mesh_compact: keep / out_rows is NULL"); return GOF_E_INVALID; }

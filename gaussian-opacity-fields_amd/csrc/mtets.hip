@@ -21,16 +21,10 @@
 // Indices at the boundary are int64 (the reference's dtype); vertex ids must be < 2^32 and 6 * #tets < 2^32 (the scans and the
 // sort count in 32 bits).  Scan and sort are the hand-written kernels of radix.hip -- no library primitives.
 #include "gof_common.h"
+#include "radix.h"
 #include <cstring>
 
 namespace gof {
-
-size_t scan_tmp_words(size_t n);
-hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
-                           const uint32_t** total_dev_out, hipStream_t stream);
-size_t rs_tmp_words(size_t n);
-hipError_t radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
-                                uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev);
 
 __constant__ int8_t MT_TRI[16][6] = {                      // tetmesh.py:23-40
     {-1,-1,-1,-1,-1,-1},{1,0,2,-1,-1,-1},{4,0,3,-1,-1,-1},{1,4,2,1,3,4},
@@ -441,6 +435,7 @@ int gof_mtets_count(int64_t V, int64_t Tt, const int64_t* tets, const float* sdf
         // ascending (min, max): stable sort by max, then stable sort by min (torch.unique(dim=0) order, tetmesh.py:110)
         const int bits = bits_for((uint64_t)(V > 0 ? V - 1 : 0));
         uint32_t *lo1 = nullptr, *hi1 = nullptr, *hi2 = nullptr, *lo2 = nullptr;
+        // (not radix.h's sort_keys63: an edge is a (lo, hi) PAIR sorted by both words, each the other's value -- no 64-bit key array, no gather)
         GOF_HIP_CHECK(radix_sort_pairs_u32(w.e_lo[0], w.e_hi[0], w.e_lo[1], w.e_hi[1], (size_t)ne, bits, w.tmp, &lo1, &hi1, stream, nullptr));
         uint32_t* hi_other = (hi1 == w.e_hi[0]) ? w.e_hi[1] : w.e_hi[0];
         uint32_t* lo_other = (lo1 == w.e_lo[0]) ? w.e_lo[1] : w.e_lo[0];

@@ -17,6 +17,8 @@
 //                 writes each digit's run contiguously at its global offset (coalesced).
 #include "gof_common.h"
 #include "gof_status.h"
+#include "radix.h"
+#include "gof_geom.h"
 
 namespace gof {
 
@@ -630,6 +632,38 @@ const uint32_t* radix_sort_error_flag(const uint32_t* tmp, size_t n, int end_bit
     const int npass = (end_bit + 7) / 8;
     if (n == 0 || npass <= 0 || rs_units(n) > OS_MAX_UNITS || npass > OS_MAX_PASSES) return nullptr;
     return tmp + OS_MAX_PASSES * RS_DIGITS + 8;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// 63-bit keys: LSD over the two words -- stable sort by the low word, gather the high words into that order, stable sort by them
+// (31 bits: bit 63 is clear).  Three units pack 3 x 21-bit cell coordinates into such keys (tsdf, cloud: thin, cloud_reg: voxel).
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+sort63_keys_lo_kernel(const u64* __restrict__ keys, uint32_t n, uint32_t* __restrict__ lo, uint32_t* __restrict__ idx)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { lo[i] = (uint32_t)keys[i]; idx[i] = i; }
+}
+__global__ void __launch_bounds__(256)
+sort63_keys_hi(const u64* __restrict__ keys, uint32_t n, const uint32_t* __restrict__ idx, uint32_t* __restrict__ hi)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) hi[i] = (uint32_t)(keys[idx[i]] >> 32);
+}
+hipError_t sort63_keys_lo(const u64* keys, size_t n, const Sort63Ws& w, hipStream_t stream)
+{
+    hipLaunchKernelGGL(sort63_keys_lo_kernel, grid_of((int64_t)n), dim3(256), 0, stream, keys, (uint32_t)n, w.lo[0], w.idx[0]);
+    return hipGetLastError();
+}
+hipError_t sort_keys63(const u64* keys, size_t n, const Sort63Ws& w, uint32_t** order, hipStream_t stream)
+{
+    uint32_t *lo1 = nullptr, *idx1 = nullptr, *hi2 = nullptr;
+    hipError_t e = radix_sort_pairs_u32(w.lo[0], w.idx[0], w.lo[1], w.idx[1], n, 32, w.tmp, &lo1, &idx1, stream, nullptr);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sort63_keys_hi, grid_of((int64_t)n), dim3(256), 0, stream, keys, (uint32_t)n, idx1, w.hi[0]);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    uint32_t* idx_other = idx1 == w.idx[0] ? w.idx[1] : w.idx[0];      // (the first sort ends in either buffer: its number of passes)
+    return radix_sort_pairs_u32(w.hi[0], idx1, w.hi[1], idx_other, n, 31, w.tmp, &hi2, order, stream, nullptr);
 }
 
 } // namespace gof

@@ -12,22 +12,17 @@
 //               same launch wrote: values are read by later launches only (workgroups do not see each other's stores in-launch);
 //   integrate:  one workgroup per frame block, 256 threads x 16 voxels, plane by plane so that every read-modify-write is coalesced;
 //               each voxel has exactly one writer per frame.
-// Mesh:  active keys sorted (stable radix sorts by the low, then the high 32 bits); a cube pass flags the edges emitted cubes use at
+// Mesh:  active keys sorted (radix.h's sort_keys63); a cube pass flags the edges emitted cubes use at
 //        their owner voxel (atomicOr; read by the next launch); per-block vertex / triangle counts and their scans (the two totals
 //        are the extraction's read-back); then the vertex and the triangle writes, a triangle finding its vertices through a per-voxel
 //        index map.  Scratch is indexed by storage slot, the output ordered by key.
 #include "gof_common.h"
+#include "radix.h"
+#include "gof_geom.h"
 #include "../../include/gof_tsdf_hip.h"
 #include "tsdf_tables.h"
 
 namespace gof {
-
-size_t scan_tmp_words(size_t n);
-hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
-                           const uint32_t** total_dev_out, hipStream_t stream);
-size_t rs_tmp_words(size_t n);
-hipError_t radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
-                                uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev);
 
 constexpr int TR = 16;                       // block resolution
 constexpr int TR3 = TR * TR * TR;
@@ -267,19 +262,6 @@ tsdf_integrate(GofTsdfVolume vol, const uint64_t* __restrict__ fkeys, const uint
 // ---------------------------------------------------------------------------------------------------------------------------
 // extraction
 // ---------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-tsdf_keys_lo(const uint64_t* __restrict__ bkeys, uint32_t n, uint32_t* __restrict__ lo, uint32_t* __restrict__ idx)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { lo[i] = (uint32_t)bkeys[i]; idx[i] = i; }
-}
-__global__ void __launch_bounds__(256)
-tsdf_keys_hi(const uint64_t* __restrict__ bkeys, uint32_t n, const uint32_t* __restrict__ idx, uint32_t* __restrict__ hi)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) hi[i] = (uint32_t)(bkeys[idx[i]] >> 32);
-}
-
 // slots of the blocks at offsets {lo..1}^3 of the workgroup's block (-1 = not active), threads [0, (2-lo)^3)
 template <int LO>
 __device__ __forceinline__ void load_neighbours(const GofTsdfVolume& vol, uint32_t slot, int* __restrict__ s_nb)
@@ -501,14 +483,7 @@ tsdf_decode(const uint64_t* __restrict__ bkeys, uint32_t n, int32_t* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------------
 // workspaces
 // ---------------------------------------------------------------------------------------------------------------------------
-template <typename T>
-static inline void carve(char*& p, T*& ptr, size_t count)
-{
-    p = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(p)));
-    ptr = reinterpret_cast<T*>(p);
-    p += count * sizeof(T);
-}
-
+// (both layouts end at the last array's unpadded end, c.off, not at Carver::total(): the sizes the ABI has always reported)
 struct FrameWs {
     uint64_t* set;       // [S] frame hash set
     uint32_t* pos;       // [S+1] flags -> their exclusive scan
@@ -521,21 +496,20 @@ static size_t frame_layout(int64_t S, void* base, FrameWs* w)
 {
     FrameWs tmp;
     FrameWs& o = w ? *w : tmp;
-    char* p = static_cast<char*>(base);
+    Carver c{ static_cast<char*>(base), 0 };
     const size_t n = (size_t)S;
-    carve(p, o.set, n);
-    carve(p, o.pos, n + 1);
-    carve(p, o.tmp, scan_tmp_words(n + 1));
-    carve(p, o.fkeys, n);
-    carve(p, o.fslots, n);
-    carve(p, o.cnt, 8);
-    return (size_t)(p - static_cast<char*>(base)) + ALIGN;
+    o.set = c.take<uint64_t>(n);
+    o.pos = c.take<uint32_t>(n + 1);
+    o.tmp = c.take<uint32_t>(scan_tmp_words(n + 1));
+    o.fkeys = c.take<uint64_t>(n);
+    o.fslots = c.take<uint32_t>(n);
+    o.cnt = c.take<uint32_t>(8);
+    return c.off + ALIGN;
 }
 
 struct ExtractWs {
-    uint32_t *lo[2], *idx[2], *hi[2];   // [n] sort buffers
+    Sort63Ws s;                         // sort buffers
     uint32_t* order;                    // [n] storage slot of every block in key order
-    uint32_t* sort_tmp;
     uint32_t* flags;                    // [n * 4096] used edges (bit = axis) at their owner voxel
     uint8_t* cases;                     // [n * 4096] cube case of emitting cubes, else 0
     int32_t* vmap;                      // [n * 4096 * 3] vertex index per voxel and axis
@@ -546,18 +520,18 @@ static size_t extract_layout(int64_t nb, void* base, ExtractWs* w)
 {
     ExtractWs tmp;
     ExtractWs& o = w ? *w : tmp;
-    char* p = static_cast<char*>(base);
+    Carver c{ static_cast<char*>(base), 0 };
     const size_t n = (size_t)nb;
-    for (int k = 0; k < 2; k++) { carve(p, o.lo[k], n); carve(p, o.idx[k], n); carve(p, o.hi[k], n); }
-    carve(p, o.order, n);
-    carve(p, o.sort_tmp, rs_tmp_words(n));
-    carve(p, o.flags, n * TR3);
-    carve(p, o.cases, n * TR3);
-    carve(p, o.vmap, n * TR3 * 3);
-    carve(p, o.bv, n + 1);
-    carve(p, o.bt, n + 1);
-    carve(p, o.scan_tmp, scan_tmp_words(n + 1));
-    return (size_t)(p - static_cast<char*>(base)) + ALIGN;
+    sort63_carve(c, n, o.s);
+    o.order = c.take<uint32_t>(n);
+    o.s.tmp = c.take<uint32_t>(rs_tmp_words(n));
+    o.flags = c.take<uint32_t>(n * TR3);
+    o.cases = c.take<uint8_t>(n * TR3);
+    o.vmap = c.take<int32_t>(n * TR3 * 3);
+    o.bv = c.take<uint32_t>(n + 1);
+    o.bt = c.take<uint32_t>(n + 1);
+    o.scan_tmp = c.take<uint32_t>(scan_tmp_words(n + 1));
+    return c.off + ALIGN;
 }
 
 static int check_volume(const GofTsdfVolume* vol)
@@ -581,8 +555,6 @@ static int check_frame(int32_t H, int32_t W, const float* depth, const float* K,
     if (!ws || ws_bytes < gof_tsdf_frame_ws_bytes(S)) { set_error("tsdf: frame workspace too small"); return GOF_E_WORKSPACE; }
     return GOF_OK;
 }
-
-static inline dim3 grid_of(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 } // namespace gof
 
@@ -625,7 +597,7 @@ int gof_tsdf_touch(const GofTsdfVolume* vol, const float* depth, int32_t H, int3
     if (int e = check_frame(H, W, depth, K, E, S, frame_ws, frame_ws_bytes)) return e;
     if (!(depth_scale > 0.f)) { set_error("tsdf: depth_scale must be > 0"); return GOF_E_INVALID; }
     FrameWs w;
-    frame_layout(S, reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(frame_ws))), &w);
+    frame_layout(S, ws_aligned(frame_ws), &w);
     GOF_HIP_CHECK(hipMemsetAsync(w.set, 0xFF, (size_t)S * sizeof(uint64_t), stream));
     GOF_HIP_CHECK(hipMemsetAsync(w.cnt, 0, 8 * sizeof(uint32_t), stream));
     hipLaunchKernelGGL(tsdf_touch, grid_of((int64_t)H * W), dim3(256), 0, stream, depth, (int)H, (int)W, K, E, depth_scale, depth_max,
@@ -662,7 +634,7 @@ int gof_tsdf_integrate(const GofTsdfVolume* vol, int64_t num_blocks, const float
     }
     if (nf == 0) return GOF_OK;
     FrameWs w;
-    frame_layout(S, reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(frame_ws))), &w);
+    frame_layout(S, ws_aligned(frame_ws), &w);
     hipLaunchKernelGGL(tsdf_activate, grid_of(nf), dim3(256), 0, stream, *vol, (uint32_t)nf, w.fkeys, w.fslots);
     GOF_LAUNCH_CHECK(stream, 0);
     hipLaunchKernelGGL(tsdf_integrate, dim3((unsigned)nf), dim3(256), 0, stream, *vol, w.fkeys, w.fslots, depth, color, (int)H, (int)W, K, E,
@@ -682,17 +654,13 @@ int gof_tsdf_extract_count(const GofTsdfVolume* vol, int64_t n, float tau, void*
     if (n == 0) return GOF_OK;
     if (!ws || ws_bytes < gof_tsdf_extract_ws_bytes(n)) { set_error("tsdf: extraction workspace too small"); return GOF_E_WORKSPACE; }
     ExtractWs w;
-    extract_layout(n, reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(ws))), &w);
-    // ascending 63-bit key: stable sort by the low 32 bits, then by the high 31 bits
-    hipLaunchKernelGGL(tsdf_keys_lo, grid_of(n), dim3(256), 0, stream, vol->block_keys, (uint32_t)n, w.lo[0], w.idx[0]);
-    GOF_LAUNCH_CHECK(stream, 0);
-    uint32_t *lo1 = nullptr, *idx1 = nullptr, *hi2 = nullptr, *idx2 = nullptr;
-    GOF_HIP_CHECK(radix_sort_pairs_u32(w.lo[0], w.idx[0], w.lo[1], w.idx[1], (size_t)n, 32, w.sort_tmp, &lo1, &idx1, stream, nullptr));
-    hipLaunchKernelGGL(tsdf_keys_hi, grid_of(n), dim3(256), 0, stream, vol->block_keys, (uint32_t)n, idx1, w.hi[0]);
-    GOF_LAUNCH_CHECK(stream, 0);
-    uint32_t* idx_other = idx1 == w.idx[0] ? w.idx[1] : w.idx[0];
-    GOF_HIP_CHECK(radix_sort_pairs_u32(w.hi[0], idx1, w.hi[1], idx_other, (size_t)n, 31, w.sort_tmp, &hi2, &idx2, stream, nullptr));
-    GOF_HIP_CHECK(hipMemcpyAsync(w.order, idx2, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    extract_layout(n, ws_aligned(ws), &w);
+    // ascending 63-bit key (tk_pack leaves bit 63 clear)
+    const u64* keys = reinterpret_cast<const u64*>(vol->block_keys);
+    uint32_t* sorted = nullptr;
+    GOF_HIP_CHECK(sort63_keys_lo(keys, (size_t)n, w.s, stream));
+    GOF_HIP_CHECK(sort_keys63(keys, (size_t)n, w.s, &sorted, stream));
+    GOF_HIP_CHECK(hipMemcpyAsync(w.order, sorted, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
     GOF_HIP_CHECK(hipMemsetAsync(w.flags, 0, (size_t)n * TR3 * sizeof(uint32_t), stream));
     hipLaunchKernelGGL(tsdf_cubes, dim3((unsigned)n), dim3(256), 0, stream, *vol, w.order, tau, w.flags, w.cases);
     GOF_LAUNCH_CHECK(stream, 0);
@@ -725,7 +693,7 @@ int gof_tsdf_extract_emit(const GofTsdfVolume* vol, int64_t n, float tau, void* 
     if (!ws || ws_bytes < gof_tsdf_extract_ws_bytes(n)) { set_error("tsdf: extraction workspace too small"); return GOF_E_WORKSPACE; }
     if (!vertices || !triangles || !colors || !normals) { set_error("tsdf: NULL output"); return GOF_E_INVALID; }
     ExtractWs w;
-    extract_layout(n, reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(ws))), &w);
+    extract_layout(n, ws_aligned(ws), &w);
     hipLaunchKernelGGL(tsdf_vertices, dim3((unsigned)n), dim3(256), 0, stream, *vol, w.order, w.flags, w.bv, (uint32_t)V, w.vmap, vertices, colors, normals);
     GOF_LAUNCH_CHECK(stream, 0);
     hipLaunchKernelGGL(tsdf_triangles, dim3((unsigned)n), dim3(256), 0, stream, *vol, w.order, w.cases, w.bt, (uint32_t)F, w.vmap, triangles);

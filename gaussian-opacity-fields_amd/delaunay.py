@@ -12,6 +12,7 @@ import ctypes as C
 import torch
 
 from diff_gaussian_rasterization import _backend as B
+import gof_native as gn
 
 __all__ = ["triangulate", "last_stats"]
 
@@ -19,14 +20,10 @@ GOF_E_CAPACITY = -5
 _STAT_NAMES = ("rounds", "exact_evaluations", "peak_cells", "slow_insertions", "located_by_scan", "distinct_points", "capacity", "live_cells")
 
 lib = B.lib
-lib.gof_delaunay_ws_bytes.restype = C.c_size_t
-lib.gof_delaunay_ws_bytes.argtypes = [C.c_int64, C.c_int64]
-lib.gof_delaunay_build.restype = C.c_int
-lib.gof_delaunay_build.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]
-lib.gof_delaunay_emit.restype = C.c_int
-lib.gof_delaunay_emit.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-lib.gof_delaunay_stats.restype = C.c_int
-lib.gof_delaunay_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+gn.bind(lib, {"gof_delaunay_ws_bytes": [C.c_int64, C.c_int64]}, {
+    "gof_delaunay_build": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p],
+    "gof_delaunay_emit": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "gof_delaunay_stats": [C.c_void_p, C.c_void_p, C.c_void_p]})
 
 # The initial arena: cells per point, learnt from the last call of at least 1024 points (its live cells, finite and infinite --
 # the arena holds both -- per point, with 10 % headroom), clamped to [6.5, 8] so that one unusual input neither starves nor inflates

@@ -12,12 +12,14 @@ deviations: the keep / drop decisions are made in fp64 instead o
 is used instead of the script's fp32 inverse of its inverse.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import torch
 
 from diff_gaussian_rasterization import _backend as B
+import gof_native as gn
 import mesh_eval
 
 __all__ = ["dilate_mask", "cull_vertices", "compact_mesh", "last_stats", "view_matrix", "DeviceMesh", "load", "cull_mesh",
@@ -38,20 +40,12 @@ assert _VIEW_DTYPE.itemsize == C.sizeof(GofCullView) == 120
 
 lib.gof_mesh_mask_row_words.restype = _i64
 lib.gof_mesh_mask_row_words.argtypes = [_i32]
-lib.gof_mesh_cull_ws_bytes.restype = _sz
-lib.gof_mesh_cull_ws_bytes.argtypes = [_i64]
-lib.gof_mesh_compact_ws_bytes.restype = _sz
-lib.gof_mesh_compact_ws_bytes.argtypes = [_i64, _i64]
-lib.gof_densify_ws_bytes.restype = _sz
-lib.gof_densify_ws_bytes.argtypes = [_i64]
-for _name, _args in {
+gn.bind(lib, {"gof_mesh_cull_ws_bytes": [_i64], "gof_mesh_compact_ws_bytes": [_i64, _i64], "gof_densify_ws_bytes": [_i64]}, {
         "gof_mesh_dilate": [_i32, _i32, _vp, _i32, _i32, _vp, _vp],
         "gof_mesh_cull": [_i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _sz, _vp],
         "gof_mesh_compact": [_i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _P64, _vp],
         "gof_compact_rows": [_i64, _vp, _vp, _vp, _vp, _sz, _P64, _vp],
-        "gof_rows_gather": [_i64, _i32, _vp, _vp, _vp, _vp, _vp]}.items():
-    getattr(lib, _name).restype = C.c_int
-    getattr(lib, _name).argtypes = _args
+        "gof_rows_gather": [_i64, _i32, _vp, _vp, _vp, _vp, _vp]})
 
 MAX_RADIUS = 31
 _last = {}
@@ -62,40 +56,14 @@ def last_stats():
     return {k: dict(v) for k, v in _last.items()}
 
 
-def _stream():
-    return B._stream()
-
-
-def _device_of(t):
-    return torch.cuda.device(t.device)
-
-
-def _on_device(t):
-    return t.device.type == "cuda"
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("mesh_cull (gfx950 backend) needs a ROCm device")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
+# the device seams, by the names the host tests replace per module (tests/test_mesh_cull_host.py); one definition each: gof_native
+_stream, _device_of, _on_device, _ptr = gn.stream, gn.device_of, gn.on_device, gn.ptr
+_device = functools.partial(gn.current_device, "mesh_cull")
 
 
 def _tensor(t, who, what, dtypes, cols=None):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError("%s: %s must be a torch tensor" % (who, what))
-    if not _on_device(t):
-        raise RuntimeError("%s (gfx950 backend) needs %s on a ROCm device, got %s" % (who, what, t.device))
-    if t.dtype not in dtypes:
-        raise RuntimeError("%s: %s must be %s, got %s" % (who, what, " or ".join(str(d) for d in dtypes), t.dtype))
-    if cols is not None and (t.dim() != 2 or t.size(1) != cols):
-        raise RuntimeError("%s: %s must have dimensions (N, %d)" % (who, what, cols))
-    if t.size(0) >= 2 ** 31 - 1:
-        raise RuntimeError("%s: at most 2^31 - 2 rows" % who)
-    return t.contiguous()
+    """gn.rows with this module's limit (gof_mesh_* take at most 2^31 - 2 rows) and its order of complaints"""
+    return gn.rows(t, who, what, dtypes, cols, limit=2 ** 31 - 1, shape_first=False, on_device=_on_device)
 
 
 # ---- (a) ----------------------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ One stated deviation: eval.py shuffles the cloud with an unseede
 """
 import contextlib
 import ctypes as C
+import functools
 import json
 import os
 import sys
@@ -21,25 +22,21 @@ import numpy as np
 import torch
 
 from diff_gaussian_rasterization import _backend as B
+import gof_native as gn
 
 __all__ = ["sample_mesh", "thin", "nearest", "last_stats", "dtu_chamfer", "read_ply", "read_ply_elements", "write_vis_ply", "main"]
 
 lib = B.lib
 _vp, _sz, _i64, _f64 = C.c_void_p, C.c_size_t, C.c_int64, C.c_double
 _P64 = C.POINTER(C.c_int64)
-for _name in ("gof_cloud_sample_ws_bytes", "gof_cloud_thin_ws_bytes", "gof_cloud_nn_index_bytes", "gof_cloud_nn_query_ws_bytes"):
-    getattr(lib, _name).restype = _sz
-    getattr(lib, _name).argtypes = [_i64]
-for _name, _args in {
+gn.bind(lib, {_name: [_i64] for _name in ("gof_cloud_sample_ws_bytes", "gof_cloud_thin_ws_bytes", "gof_cloud_nn_index_bytes", "gof_cloud_nn_query_ws_bytes")}, {
         "gof_cloud_sample_count": [_i64, _vp, _i64, _vp, _f64, _vp, _sz, _P64, _vp],
         "gof_cloud_sample_emit": [_i64, _vp, _i64, _vp, _f64, _vp, _sz, _i64, _vp, _vp],
         "gof_cloud_thin": [_i64, _vp, _f64, _vp, _vp, _sz, _P64, _vp],
         "gof_cloud_thin_stats": [_vp, _vp, _vp],
         "gof_cloud_nn_build": [_i64, _vp, _vp, _sz, _vp],
         "gof_cloud_nn_query": [_i64, _vp, _sz, _i64, _vp, _vp, _vp, _vp, _sz, _vp],
-        "gof_cloud_nn_stats": [_vp, _vp, _vp]}.items():
-    getattr(lib, _name).restype = C.c_int
-    getattr(lib, _name).argtypes = _args
+        "gof_cloud_nn_stats": [_vp, _vp, _vp]})
 
 _last = {}
 
@@ -50,34 +47,13 @@ def last_stats():
     return {k: dict(v) for k, v in _last.items()}
 
 
-def _stream():
-    return B._stream()
-
-
-def _device_of(t):
-    return torch.cuda.device(t.device)
-
-
-def _on_device(t):
-    return t.device.type == "cuda"
+# the device seams, by the names the host tests replace per module (tests/test_mesh_eval_host.py); one definition each: gof_native
+_stream, _device_of, _on_device, _ptr = gn.stream, gn.device_of, gn.on_device, gn.ptr
+_device = functools.partial(gn.current_device, "mesh_eval")
 
 
 def _cloud(t, who, what="points", dtype=torch.float64):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError("%s: %s must be a torch tensor" % (who, what))
-    if t.dim() != 2 or t.size(1) != 3:
-        raise RuntimeError("%s: %s must have dimensions (N, 3)" % (who, what))
-    if not _on_device(t):
-        raise RuntimeError("%s (gfx950 backend) needs %s on a ROCm device, got %s" % (who, what, t.device))
-    if t.dtype != dtype:
-        raise RuntimeError("%s: %s must be %s, got %s" % (who, what, dtype, t.dtype))
-    if t.size(0) >= 2 ** 31:
-        raise RuntimeError("%s: at most 2^31 - 1 rows" % who)
-    return t.contiguous()
-
-
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
+    return gn.rows(t, who, what, dtype, on_device=_on_device)
 
 
 def sample_mesh(vertices, triangles, thresh):
@@ -294,12 +270,6 @@ def _vis_colors(n, index, dist, vis_dist, max_dist, device):
     color[index] = R * alpha + W * (1 - alpha)
     color[index[dist >= max_dist]] = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64, device=device)
     return color
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("mesh_eval (gfx950 backend) needs a ROCm device")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def main(argv=None):

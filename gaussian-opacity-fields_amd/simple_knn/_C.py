@@ -5,12 +5,10 @@ import ctypes as C
 import torch
 
 from diff_gaussian_rasterization import _backend as _B
+import gof_native as gn
 
 lib = _B.lib
-lib.gof_knn_ws_bytes.restype = C.c_size_t
-lib.gof_knn_ws_bytes.argtypes = [C.c_int64]
-lib.gof_knn_mean_dist3.restype = C.c_int
-lib.gof_knn_mean_dist3.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+gn.bind(lib, {"gof_knn_ws_bytes": [C.c_int64]}, {"gof_knn_mean_dist3": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]})
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:

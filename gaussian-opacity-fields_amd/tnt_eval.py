@@ -15,6 +15,7 @@ points, normals are not estimated.
 """
 import contextlib
 import ctypes as C
+import functools
 import json
 import os
 import sys
@@ -23,6 +24,7 @@ import numpy as np
 import torch
 
 from diff_gaussian_rasterization import _backend as B
+import gof_native as gn
 import mesh_eval
 
 __all__ = ["read_crop_volume", "read_log_trajectory", "crop", "voxel_down_sample", "uniform_down_sample", "transform_points", "icp",
@@ -38,17 +40,12 @@ MAX_POLYGON = 4096
 lib = B.lib
 _vp, _sz, _i64, _f64, _int = C.c_void_p, C.c_size_t, C.c_int64, C.c_double, C.c_int
 _P64 = C.POINTER(C.c_int64)
-for _name in ("gof_cloud_transform_ws_bytes", "gof_cloud_crop_ws_bytes", "gof_cloud_voxel_ws_bytes", "gof_cloud_icp_sums_ws_bytes"):
-    getattr(lib, _name).restype = _sz
-    getattr(lib, _name).argtypes = [_i64]
-for _name, _args in {
+gn.bind(lib, {_name: [_i64] for _name in ("gof_cloud_transform_ws_bytes", "gof_cloud_crop_ws_bytes", "gof_cloud_voxel_ws_bytes", "gof_cloud_icp_sums_ws_bytes")}, {
         "gof_cloud_transform": [_i64, _vp, _vp, _vp, _vp, _sz, _vp],
         "gof_cloud_crop": [_i64, _vp, _vp, _int, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _sz, _P64, _vp],
         "gof_cloud_voxel": [_i64, _vp, _f64, _vp, _vp, _vp, _sz, _P64, _vp],
         "gof_cloud_icp_sums1": [_i64, _vp, _i64, _vp, _vp, _vp, _f64, _vp, _sz, _P64, _vp, _vp],
-        "gof_cloud_icp_sums2": [_i64, _vp, _i64, _vp, _vp, _vp, _f64, _vp, _vp, _sz, _vp, _vp]}.items():
-    getattr(lib, _name).restype = C.c_int
-    getattr(lib, _name).argtypes = _args
+        "gof_cloud_icp_sums2": [_i64, _vp, _i64, _vp, _vp, _vp, _f64, _vp, _vp, _sz, _vp, _vp]})
 
 _last = {}
 
@@ -58,40 +55,13 @@ def last_stats():
     return {k: dict(v) for k, v in _last.items()}
 
 
-def _stream():
-    return B._stream()
+# the device seams, by the names the host tests replace per module (tests/test_tnt_eval_host.py); one definition each: gof_native
+_stream, _device_of, _on_device, _ptr = gn.stream, gn.device_of, gn.on_device, gn.ptr
+_device = functools.partial(gn.current_device, "tnt_eval")
 
 
-def _device_of(t):
-    return torch.cuda.device(t.device)
-
-
-def _on_device(t):
-    return t.device.type == "cuda"
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("tnt_eval (gfx950 backend) needs a ROCm device")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _cloud(t, who, what="points"):
-    if not isinstance(t, torch.Tensor):
-        raise RuntimeError("%s: %s must be a torch tensor" % (who, what))
-    if t.dim() != 2 or t.size(1) != 3:
-        raise RuntimeError("%s: %s must have dimensions (N, 3)" % (who, what))
-    if not _on_device(t):
-        raise RuntimeError("%s (gfx950 backend) needs %s on a ROCm device, got %s" % (who, what, t.device))
-    if t.dtype != torch.float64:
-        raise RuntimeError("%s: %s must be torch.float64, got %s" % (who, what, t.dtype))
-    if t.size(0) >= 2 ** 31:
-        raise RuntimeError("%s: at most 2^31 - 1 rows" % who)
-    return t.contiguous()
-
-
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
+def _cloud(t, who, what="points", dtype=torch.float64):
+    return gn.rows(t, who, what, dtype, on_device=_on_device)
 
 
 def _matrix(m, who):

@@ -5,6 +5,7 @@ import ctypes as C
 import torch
 
 from diff_gaussian_rasterization import _backend as _B
+import gof_native as gn
 
 lib = _B.lib
 _check = _B._check
@@ -23,26 +24,16 @@ class GofAdamTensor(C.Structure):
 def _declare():
     vp, sz, i32, f32 = C.c_void_p, C.c_size_t, C.c_int32, C.c_float
     W11 = C.POINTER(C.c_float)
-    lib.gof_ssim_scratch_bytes.restype = sz
-    lib.gof_ssim_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.gof_ssim_forward.argtypes = [i32, i32, i32, vp, vp, W11, vp, vp, vp, sz, vp]
-    lib.gof_ssim_backward.argtypes = [i32, i32, i32, vp, vp, W11, vp, vp, vp, vp]
-    lib.gof_depth_to_normal.argtypes = [i32, i32, vp, vp, f32, f32, vp, vp, vp]
-    lib.gof_depth_to_normal_backward.argtypes = [i32, i32, vp, vp, f32, f32, vp, vp, vp, vp]
-    lib.gof_adam_step.argtypes = [i32, C.POINTER(GofAdamTensor), C.c_double, C.c_double, C.c_double, vp]
-    lib.gof_l1_scratch_bytes.restype = sz
-    lib.gof_l1_scratch_bytes.argtypes = [C.c_uint64]
-    lib.gof_l1_forward.argtypes = [C.c_uint64, vp, vp, vp, vp, sz, vp]
-    lib.gof_l1_backward.argtypes = [C.c_uint64, vp, vp, vp, vp, vp]
-    lib.gof_l1_forward.restype = lib.gof_l1_backward.restype = C.c_int
-    lib.gof_train_loss_scratch_bytes.restype = sz
-    lib.gof_train_loss_scratch_bytes.argtypes = [i32, i32]
-    lib.gof_train_loss.argtypes = [i32, i32, vp, vp, W11, vp, f32, f32, C.c_double, C.c_double, C.c_double, vp, vp, vp, sz, vp]
-    lib.gof_train_loss.restype = C.c_int
-    lib.gof_rot3_apply.argtypes = [C.c_int64, vp, i32, i32, i32, vp, vp, vp]
-    lib.gof_rot3_apply.restype = C.c_int
-    for n in ("gof_ssim_forward", "gof_ssim_backward", "gof_depth_to_normal", "gof_depth_to_normal_backward", "gof_adam_step"):
-        getattr(lib, n).restype = C.c_int
+    gn.bind(lib, {"gof_ssim_scratch_bytes": [i32, i32, i32], "gof_l1_scratch_bytes": [C.c_uint64], "gof_train_loss_scratch_bytes": [i32, i32]}, {
+        "gof_ssim_forward": [i32, i32, i32, vp, vp, W11, vp, vp, vp, sz, vp],
+        "gof_ssim_backward": [i32, i32, i32, vp, vp, W11, vp, vp, vp, vp],
+        "gof_depth_to_normal": [i32, i32, vp, vp, f32, f32, vp, vp, vp],
+        "gof_depth_to_normal_backward": [i32, i32, vp, vp, f32, f32, vp, vp, vp, vp],
+        "gof_adam_step": [i32, C.POINTER(GofAdamTensor), C.c_double, C.c_double, C.c_double, vp],
+        "gof_l1_forward": [C.c_uint64, vp, vp, vp, vp, sz, vp],
+        "gof_l1_backward": [C.c_uint64, vp, vp, vp, vp, vp],
+        "gof_train_loss": [i32, i32, vp, vp, W11, vp, f32, f32, C.c_double, C.c_double, C.c_double, vp, vp, vp, sz, vp],
+        "gof_rot3_apply": [C.c_int64, vp, i32, i32, i32, vp, vp, vp]})
 
 
 _declare()

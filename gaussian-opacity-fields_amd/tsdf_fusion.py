@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from diff_gaussian_rasterization import _backend as B
+import gof_native as gn
 
 __all__ = ["TSDFVolume", "TriangleMesh", "fuse_views", "write_ply", "tsdf_fusion"]
 
@@ -42,21 +43,14 @@ def bind(lib):
     vp, sz, i32, i64, f32 = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_float
     V = C.POINTER(GofTsdfVolume)
     P = C.POINTER(i64)
-    for name, args in (("gof_tsdf_frame_ws_bytes", [i64]), ("gof_tsdf_extract_ws_bytes", [i64])):
-        getattr(lib, name).restype = sz
-        getattr(lib, name).argtypes = args
-    sigs = {
+    return gn.bind(lib, {"gof_tsdf_frame_ws_bytes": [i64], "gof_tsdf_extract_ws_bytes": [i64]}, {
         "gof_tsdf_grow": [V, V, i64, vp],
         "gof_tsdf_touch": [V, vp, i32, i32, vp, vp, f32, f32, vp, sz, i64, P, P, vp],
         "gof_tsdf_integrate": [V, i64, vp, vp, i32, i32, vp, vp, f32, f32, vp, sz, i64, i64, i64, vp],
         "gof_tsdf_extract_count": [V, i64, f32, vp, sz, P, P, vp],
         "gof_tsdf_extract_emit": [V, i64, f32, vp, sz, i64, i64, vp, vp, vp, vp, vp],
         "gof_tsdf_block_coords": [V, i64, vp, vp],
-    }
-    for name, args in sigs.items():
-        getattr(lib, name).argtypes = args
-        getattr(lib, name).restype = C.c_int
-    return lib
+    })
 
 
 bind(B.lib)

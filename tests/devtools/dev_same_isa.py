@@ -2,7 +2,9 @@
 revision?  (An edit under a developer-only #ifdef -- GOF_STATS, GOF_TILE_CLOCK -- changes the source hash bench.py labels the committed
 PMC pass with, not the kernels the pass measured.)  Compiles both states of csrc/blend_{forward,backward}.hip with the product's flags
 to device assembly and compares it, ignoring the per-source `__hip_cuid_*` symbol, file names and line tables.
-    python tests/devtools/dev_same_isa.py <git-rev> [--record]     # --record: add the current source hash to the PMC file's _same_isa_sha16
+    python tests/devtools/dev_same_isa.py <git-rev> [--record] [unit.hip ...]     # --record: add the current source hash to the PMC file's _same_isa_sha16
+With file names (of csrc/) those units are compared instead of the two blend kernels: the proof that an edit of a unit's host code or
+of its includes left its device code alone.
 No GPU needed (hipcc cross-compiles)."""
 import json
 import os
@@ -29,9 +31,11 @@ def asm_of(path_in_csrc):
 
 def main():
     rev = sys.argv[1]
+    if "--record" in sys.argv and any(a.endswith(".hip") for a in sys.argv[2:]):
+        sys.exit("--record is about the two blend kernels' PMC file: not with file names")
     same = True
     same_by = {}
-    for f in FILES:
+    for f in [a for a in sys.argv[2:] if a.endswith(".hip")] or FILES:
         cur = asm_of(os.path.join(CSRC, f))
         tmp = os.path.join(CSRC, "_same_isa_tmp_" + f)          # (inside csrc so that the relative includes resolve; headers: working tree)
         try:
@@ -44,8 +48,11 @@ def main():
         same &= ok
         same_by[f[:-4]] = ok
         print("%-22s %s (%d lines of device assembly)" % (f, "identical" if ok else "DIFFERENT", len(cur)))
-    hdr = subprocess.run(["git", "-C", ROOT, "diff", "--quiet", rev, "--", "gaussian-opacity-fields_amd/csrc/gof_common.h"]).returncode == 0
-    print("gof_common.h           %s since %s" % ("unchanged" if hdr else "CHANGED (the comparison above used the working tree's header for both states)", rev))
+    hdr = True
+    for h in ("gof_common.h", "radix.h"):                      # the headers the training step's units include (a header that is new since rev counts as changed)
+        ok = subprocess.run(["git", "-C", ROOT, "diff", "--quiet", rev, "--", "gaussian-opacity-fields_amd/csrc/" + h]).returncode == 0
+        hdr &= ok
+        print("%-22s %s since %s" % (h, "unchanged" if ok else "CHANGED (the comparison above used the working tree's header for both states)", rev))
     if hdr and "--record" in sys.argv:
         import bench
         f = os.path.join(ROOT, "profiles", bench.PMC_FILE)

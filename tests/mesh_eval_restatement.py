@@ -138,3 +138,44 @@ def dtu_chamfer(data_pcd, perm, obs_mask, bb, res, plane, stl, thresh=0.2, patch
     return {"mean_d2s": float(mean_d2s), "mean_s2d": float(mean_s2d), "overall": float((mean_d2s + mean_s2d) / 2),
             "data_down": data_down, "dist_d2s": dist_d2s, "idx_d2s": idx_d2s, "d2s_index": np.where(inbound)[0][grid_inbound][in_obs],
             "dist_s2d": dist_s2d, "idx_s2d": idx_s2d, "s2d_index": np.where(above)[0]}
+
+
+# ---- a test cloud for the sort of the 3 x 21-bit cell keys (shared by the thinning and the voxel tests) ----------------------------
+def straddle_cloud(n=5000, edge=0.5, seed=17):
+    """A cloud for the sort of the 3 x 21-bit cell keys (x << 42 | y << 21 | z) that thin and voxel_down_sample share: the key's low
+    word holds z and y's bits 0..10, its high word x and y's bits 11..20.  n points in 240 cells of edge `edge`: x in 0..3, z in 0..5,
+    y in 0..3, 2046..2049 and 4095..4096 -- y straddles 2048 (bit 32 of the key) and 4096, so that cells agree in one word and differ
+    in the other, in both directions; ~20 points per cell, in random order (a stable sort keeps them in input order).  More than one
+    256-lane workgroup and more than one radix tile."""
+    rng = np.random.default_rng(seed)
+    ys = np.array([0, 1, 2, 3, 2046, 2047, 2048, 2049, 4095, 4096])
+    cells = np.stack([rng.integers(0, 4, n), ys[rng.integers(0, len(ys), n)], rng.integers(0, 6, n)], -1)
+    cells[0], cells[1] = (0, 0, 0), (3, 4096, 5)                       # the corners: the extent does not depend on the draws
+    P = (cells + rng.uniform(0.3, 0.7, (n, 3))) * edge
+    P[0] = 0.0                                                         # the minimum, on the lattice
+    return np.ascontiguousarray(P)
+
+
+def key_words(cells):
+    """(low, high) 32-bit words of the keys of integer cells (n, 3)"""
+    c = np.asarray(cells).astype(np.uint64)
+    key = (c[:, 0] << np.uint64(42)) | (c[:, 1] << np.uint64(21)) | c[:, 2]
+    return (key & np.uint64(0xFFFFFFFF)).astype(np.int64), (key >> np.uint64(32)).astype(np.int64)
+
+
+def check_straddle(P, cells):
+    """the preconditions of the units and what the case is for (see straddle_cloud); cells: floor coordinates as the unit forms them"""
+    assert np.isfinite(P).all() and len(P) > 4096
+    assert cells.min() >= 0 and cells.max() <= 2 ** 21 - 1
+    y = cells[:, 1]
+    assert (y < 2048).any() and (y >= 2048).any() and len(np.unique(cells[:, 0])) > 1
+    lo, hi = key_words(cells)
+    pairs = np.unique(np.stack([lo, hi], -1), axis=0)
+    assert len(pairs) < len(P) / 4                                     # duplicated cells
+    by_lo, by_hi = {}, {}
+    for a, b in pairs.tolist():
+        by_lo.setdefault(a, set()).add(b)
+        by_hi.setdefault(b, set()).add(a)
+    assert max(len(v) for v in by_lo.values()) > 1 and max(len(v) for v in by_hi.values()) > 1      # equal low / different high, and the reverse
+    order_lo = np.argsort(lo, kind="stable")
+    assert not (np.diff(hi[order_lo]) >= 0).all()                      # the two words disagree about the order

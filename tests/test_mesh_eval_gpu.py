@@ -70,13 +70,12 @@ def test_sampling_a_marching_cubes_mesh():
     assert np.array_equal(bits(got[len(V):]), bits(want))
 
 
-@pytest.mark.parametrize("name", ["rand1", "rand2", "rand3", "morton", "dups", "lattice", "n0", "n1"])
+@pytest.mark.parametrize("name", H.THIN_CASES)
 def test_thinning_equals_the_sequential_loop(name):
     import mesh_eval as M
     P, r = H.thin_case(name)
     want = R.thin(P, r)
-    if name.startswith("rand") or name == "morton":
-        assert R.pairs_near_radius(P, r) == 0
+    H.check_thin_case(name, P, r)
     got = M.thin(dev(P), r).cpu().numpy()
     assert np.array_equal(got, want), "%d of %d points differ" % ((got != want).sum(), len(P))
     assert M.last_stats()["thin"]["kept"] == want.sum()

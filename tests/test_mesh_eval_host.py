@@ -69,6 +69,8 @@ def thin_case(name):
     """-> (points in visiting order, r)"""
     if name in ("n0", "n1"):
         return np.zeros((int(name[1]), 3)) + 0.25, 0.5
+    if name == "straddle":
+        return R.straddle_cloud(), 0.5
     if name == "lattice":
         g = np.arange(16, dtype=np.float64) * 0.5              # exact in binary: every neighbour pair is an equality of the <=
         L = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
@@ -290,12 +292,22 @@ def test_bad_meshes_are_refused(name, tmp_path):
     assert ("not finite" in err) if name == "nan" else ("outside" in err), err
 
 
-@pytest.mark.parametrize("name", ["rand1", "rand2", "rand3", "morton", "dups", "lattice", "n0", "n1"])
+THIN_CASES = ["rand1", "rand2", "rand3", "morton", "dups", "lattice", "n0", "n1", "straddle"]
+
+
+def check_thin_case(name, P, r):
+    """what a case promises before anything is compared"""
+    if name.startswith("rand") or name in ("morton", "straddle"):
+        assert R.pairs_near_radius(P, r) == 0          # no pair within 4 ulp of r^2: nothing may be left out of the comparison
+    if name == "straddle":
+        R.check_straddle(P, np.floor((P - P.min(0)) / (r * (1.0 + 1.0 / 1048576.0))).astype(np.int64))      # thin's cells (DESIGN.md 3.8)
+
+
+@pytest.mark.parametrize("name", THIN_CASES)
 def test_thinning_equals_the_sequential_loop(name, tmp_path):
     P, r = thin_case(name)
     want = R.thin(P, r)
-    if name.startswith("rand") or name == "morton":
-        assert R.pairs_near_radius(P, r) == 0          # no pair within 4 ulp of r^2: nothing may be left out of the comparison
+    check_thin_case(name, P, r)
     res = _emulate("thin:" + name, tmp_path)
     assert np.array_equal(res["keep"], want), "%d of %d points differ" % ((res["keep"] != want).sum(), len(P))
     st = json.loads(str(res["stats"]))

@@ -114,6 +114,9 @@ def voxel_case(name):
     rng = np.random.default_rng(13)
     if name in ("n0", "n1"):
         return np.zeros((int(name[1]), 3)) + 0.25, 0.5
+    if name == "straddle":                                       # the 63-bit key sort where its two words disagree
+        from mesh_eval_restatement import straddle_cloud
+        return straddle_cloud(), 0.5
     if name == "surface":
         return surface(40000, 3), 0.5
     if name == "one":
@@ -408,6 +411,10 @@ def check_voxel(name, res):
         assert len(counts) == 1
     if name == "lattice":
         assert len(counts) == 11 ** 3 and counts.max() == 8 and counts.min() == 1      # (the origin lies half a voxel below the minimum)
+    if name == "straddle":
+        from mesh_eval_restatement import check_straddle
+        check_straddle(P, np.floor((P - (P.min(0) - 0.5 * v)) / v).astype(np.int64))    # the voxels
+        assert counts.max() > 1
     assert res["points"].shape == want.shape, "%d voxels, the restatement has %d" % (len(res["points"]), len(want))
     assert np.array_equal(res["counts"], counts)
     assert np.array_equal(bits(res["points"]), bits(want))
@@ -469,7 +476,7 @@ def check_fscore(res, want):
 
 
 CROP_CASES = ["circle_z_moved", "poly_x_plain", "poly_y_plain", "poly_z_plain", "poly_x_moved", "poly_z_moved", "nopoly_z_plain", "empty_z_plain"]
-VOXEL_CASES = ["surface", "one", "lattice", "skew", "n0", "n1"]
+VOXEL_CASES = ["surface", "one", "lattice", "skew", "n0", "n1", "straddle"]
 SUMS_CASES = ["torus", "pow2", "ragged", "n0", "n1", "single"]
 
 
