@@ -940,6 +940,52 @@ static int compact(DtWs& w, int& active, uint32_t* ncells, uint32_t npts, hipStr
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// test support: the predicates on caller-chosen index tuples (gof_debug_delaunay_predicates)
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int DT_PROBE_OPS = 7;
+constexpr uint32_t DT_PROBE_BAD = 0x80000000u;                 // err[0] while the indices are checked: a query is out of range
+
+__host__ __device__ inline int probe_indices(int op) { return op == 4 ? 3 : (op == 0 || op == 2) ? 4 : 5; }
+
+// flags (in err[0], cleared before) a query whose indices the op would read outside [0, n_points), or whose dk is no vertex slot
+__global__ void __launch_bounds__(DT_THREADS) dt_probe_check(uint32_t npts, uint32_t nq, const int32_t* __restrict__ idx, int op,
+                                                              uint32_t* __restrict__ err)
+{
+    const uint32_t q = blockIdx.x * DT_THREADS + threadIdx.x;
+    if (q >= nq) return;
+    bool bad = false;
+    for (int k = 0; k < probe_indices(op); k++) bad |= (uint32_t)idx[6 * (size_t)q + k] >= npts;
+    if (op == 6) bad |= (uint32_t)idx[6 * (size_t)q + 5] >= 4u;
+    if (bad) atomicOr(&err[0], DT_PROBE_BAD);
+}
+
+// one query per thread, with a Pred of its own: the exact evaluations count into the thread's LDS word, the error bits into err[q]
+__global__ void __launch_bounds__(DT_THREADS) dt_probe(const float* __restrict__ xyz, uint32_t nq, const int32_t* __restrict__ idx, int op,
+                                                        int32_t* __restrict__ sign, uint32_t* __restrict__ exact, uint32_t* __restrict__ err)
+{
+    __shared__ unsigned long long s_exact[DT_THREADS];
+    const uint32_t q = blockIdx.x * DT_THREADS + threadIdx.x;
+    if (q >= nq) return;
+    s_exact[threadIdx.x] = 0;
+    const Pred P = {xyz, &s_exact[threadIdx.x], &err[q]};
+    const int32_t* t = idx + 6 * (size_t)q;
+    const uint32_t a = (uint32_t)t[0], b = (uint32_t)t[1], c = (uint32_t)t[2], d = (uint32_t)t[3], e = (uint32_t)t[4];
+    int s = 0;
+    switch (op) {
+    case 0: s = dt::orient(P, a, b, c, d); break;
+    case 1: s = dt::insphere(P, a, b, c, d, e); break;
+    case 2: s = dt::orient_exact(P, a, b, c, d); break;
+    case 3: s = dt::insphere_exact(P, a, b, c, d, e); break;
+    case 4: s = collinear(P, a, b, c) ? 1 : 0; break;
+    case 5: s = insphere_perturbed(P, make_int4((int)a, (int)b, (int)c, (int)d), e, &err[q]); break;
+    default: s = incircle_perturbed(P, make_int4((int)a, (int)b, (int)c, (int)d), t[5], e, &err[q]); break;
+    }
+    sign[q] = s;
+    const unsigned long long n = s_exact[threadIdx.x];
+    exact[q] = n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
+}
+
 } // namespace gof
 
 using namespace gof;
@@ -1153,5 +1199,34 @@ extern "C" int gof_delaunay_stats(const void* ws, int64_t* stats, void* stream)
     DtHeader h;
     if (int r = built_layout(ws, &w, &h, st)) return r;
     for (int k = 0; k < 8; k++) stats[k] = h.stats[k];
+    return 0;
+}
+
+// Test support (include/gof_delaunay_hip.h): the build's own predicate functions on index tuples the caller chooses.
+extern "C" int gof_debug_delaunay_predicates(int64_t n_points, const float* xyz, int64_t n_queries, const int32_t* idx, int op, int32_t* sign,
+                                             uint32_t* exact, uint32_t* err, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (op < 0 || op >= DT_PROBE_OPS) { set_error("delaunay probe: unknown op %d", op); return GOF_E_INVALID; }
+    if (n_points < 0 || n_points >= ((int64_t)1 << 31) || n_queries < 0 || n_queries >= ((int64_t)1 << 31)) {
+        set_error("delaunay probe: n_points = %lld, n_queries = %lld must be in [0, 2^31)", (long long)n_points, (long long)n_queries);
+        return GOF_E_INVALID;
+    }
+    if (n_queries == 0) return 0;
+    if (!xyz || !idx || !sign || !exact || !err) { set_error("delaunay probe: a pointer is NULL"); return GOF_E_INVALID; }
+    const uint32_t nq = (uint32_t)n_queries;
+    hipLaunchKernelGGL(dt_fill, dim3(blocks(nq)), dim3(DT_THREADS), 0, st, nq, err, 0u);
+    hipLaunchKernelGGL(dt_probe_check, dim3(blocks(nq)), dim3(DT_THREADS), 0, st, (uint32_t)n_points, nq, idx, op, err);
+    uint32_t flag = 0;
+    GOF_HIP_CHECK(hipMemcpyAsync(&flag, err, 4, hipMemcpyDeviceToHost, st));
+    GOF_HIP_CHECK(hipStreamSynchronize(st));
+    if (flag & DT_PROBE_BAD) {
+        hipLaunchKernelGGL(dt_fill, dim3(1), dim3(DT_THREADS), 0, st, 1u, err, 0u);
+        GOF_HIP_CHECK(hipGetLastError());
+        set_error("delaunay probe: a query of op %d holds an index outside [0, %lld) (or a vertex slot outside [0, 4))", op, (long long)n_points);
+        return GOF_E_INVALID;
+    }
+    hipLaunchKernelGGL(dt_probe, dim3(blocks(nq)), dim3(DT_THREADS), 0, st, xyz, nq, idx, op, sign, exact, err);
+    GOF_HIP_CHECK(hipGetLastError());
     return 0;
 }

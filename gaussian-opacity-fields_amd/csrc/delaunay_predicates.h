@@ -11,7 +11,7 @@
 namespace gof {
 namespace dt {
 
-constexpr int XN = 128;                      // expansion capacity of the exact paths (compressed lengths stay far below it)
+constexpr int XN = 128;                      // expansion capacity of the exact paths (tests/test_delaunay_predicates_*: never outgrown)
 constexpr double ORIENT_ERR = 2.0e-15;       // ~18 eps (Shewchuk o3derrboundA = 7 eps, + 3 eps for the rounded differences)
 constexpr double INSPHERE_ERR = 5.0e-15;     // ~45 eps (isperrboundA = 16 eps, + 5 eps for the rounded differences)
 constexpr double TINY = 1e-250;              // below it the fp64 filter could lose bits to underflow: always exact

@@ -39,6 +39,24 @@ int gof_delaunay_emit(void* ws, int64_t num_tets, int32_t* tets_out, void* strea
  * insertions, [4] points located by a global scan, [5] distinct points, [6] cell capacity, [7] live cells (finite and infinite). */
 int gof_delaunay_stats(const void* ws, int64_t* stats, void* stream);
 
+/* ---- test support (the debug family, like gof_debug_fetch): not part of the product's contract, may change with the tests ----
+ *
+ * Runs one of the build's own predicate functions on n_queries index tuples idx [n_queries][6] = (a, b, c, d, e, aux) into
+ * xyz [n_points][3] (fp32), one thread per query, no workspace:
+ *   op 0  orient(a, b, c, d)            sign det[b - a, c - a, d - a], fp64 filter first
+ *   op 1  insphere(a, b, c, d, e)       > 0: e inside the sphere of the positive (a, b, c, d); 0: on it
+ *   op 2  orient_exact, op 3 insphere_exact: the expansion arithmetic without the filter
+ *   op 4  collinear(a, b, c)            1: collinear, 0: not
+ *   op 5  insphere_perturbed(cell (a, b, c, d), p = e)         the cell positively oriented; never 0
+ *   op 6  incircle_perturbed(fin = (a, b, c, d), dk = aux, p = e)   fin positive, aux in [0, 4) its vertex off the face, p in the
+ *         face's plane; never 0
+ * Every query fully writes sign[q], exact[q] (the exact evaluations it made) and err[q] (the DTE_* bits it raised: 1 = an
+ * expansion outgrew its buffer, 32 = the perturbation did not decide).  All pointers are device pointers.  GOF_E_INVALID for a NULL
+ * pointer, an unknown op, or a query whose indices -- those its op reads -- lie outside [0, n_points); nothing is read out of
+ * range.  Synchronises `stream`. */
+int gof_debug_delaunay_predicates(int64_t n_points, const float* xyz, int64_t n_queries, const int32_t* idx, int op, int32_t* sign,
+                                  uint32_t* exact, uint32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
