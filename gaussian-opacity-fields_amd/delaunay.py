@@ -32,9 +32,13 @@ _CPP_MIN, _CPP_MAX = 6.5, 8.0
 _cells_per_point = 7.0
 _last = {}
 
+# the device seams, by the names the host tests replace per module (tests/test_delaunay_host.py); one definition each: gof_native
+_stream, _device_of, _on_device = gn.stream, gn.device_of, gn.on_device
+
 
 def last_stats():
-    """Statistics of the last triangulate call: rounds, exact predicate evaluations, peak arena cells and bytes, ..."""
+    """Statistics of the last triangulate call: rounds, exact predicate evaluations, peak arena cells and bytes, ..., and how often it
+    started over with a larger arena ("retries")"""
     return dict(_last)
 
 
@@ -45,7 +49,7 @@ def triangulate(points: torch.Tensor, capacity: int = None) -> torch.Tensor:
     global _cells_per_point
     if points.dim() != 2 or points.size(1) != 3:
         raise RuntimeError("triangulate: points must have dimensions (num_points, 3)")
-    if points.device.type != "cuda":
+    if not _on_device(points):
         raise RuntimeError("triangulate (gfx950 backend) needs the points on a ROCm device, got %s" % points.device)
     if points.dtype != torch.float32:
         raise RuntimeError("triangulate: expected a float32 tensor, got %s" % points.dtype)
@@ -55,26 +59,28 @@ def triangulate(points: torch.Tensor, capacity: int = None) -> torch.Tensor:
         raise RuntimeError("triangulate: at most 2^31 - 1 points")
     cap = int(capacity) if capacity else int(_cells_per_point * n) + 64
     cap = max(16, min(cap, 2 ** 30 - 1))
-    with torch.cuda.device(pts.device):
+    retries = 0
+    with _device_of(pts):
         while True:
             nb = lib.gof_delaunay_ws_bytes(n, cap)
             ws = torch.empty(nb, dtype=torch.uint8, device=pts.device)
             m = C.c_int64()
-            rc = lib.gof_delaunay_build(n, pts.data_ptr(), cap, ws.data_ptr(), nb, C.byref(m), B._stream())
+            rc = lib.gof_delaunay_build(n, pts.data_ptr(), cap, ws.data_ptr(), nb, C.byref(m), _stream())
             if rc == GOF_E_CAPACITY and m.value > cap:
                 del ws
-                cap = int(m.value)
+                cap, retries = int(m.value), retries + 1
                 continue
             B._check(rc)
             break
         out = torch.empty((m.value, 4), dtype=torch.int32, device=pts.device)
-        B._check(lib.gof_delaunay_emit(ws.data_ptr(), m.value, out.data_ptr() if m.value else None, B._stream()))
+        B._check(lib.gof_delaunay_emit(ws.data_ptr(), m.value, out.data_ptr() if m.value else None, _stream()))
         st = (C.c_int64 * 8)()
-        B._check(lib.gof_delaunay_stats(ws.data_ptr(), st, B._stream()))
+        B._check(lib.gof_delaunay_stats(ws.data_ptr(), st, _stream()))
     _last.clear()
     _last.update(zip(_STAT_NAMES, list(st)))
     _last["workspace_bytes"] = int(nb)
     _last["cells"] = int(m.value)
+    _last["retries"] = retries
     if n >= 1024 and _last["live_cells"] > 0:
         _cells_per_point = min(_CPP_MAX, max(_CPP_MIN, 1.1 * _last["live_cells"] / n))
     return out

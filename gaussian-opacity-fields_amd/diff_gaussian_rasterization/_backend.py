@@ -110,9 +110,17 @@ def is_in_grad_bucket(t):
     return st is not None and t.untyped_storage() is st and lo <= t.data_ptr() and t.data_ptr() + t.numel() * t.element_size() <= hi
 
 
+class GofError(RuntimeError):
+    """A non-zero status of the library: the message is gof_last_error(), .code the status (a GOF_E_* of include/gof_hip.h)"""
+
+    def __init__(self, code, message):
+        super().__init__(message)
+        self.code = code
+
+
 def _check(rc):
     if rc != 0:
-        raise RuntimeError("libgof_hip: " + lib.gof_last_error().decode(errors="replace"))
+        raise GofError(rc, "libgof_hip: " + lib.gof_last_error().decode(errors="replace"))
 
 
 def _ptr(t):

@@ -1,8 +1,9 @@
 """What the ctypes front ends of libgof_hip.so share (mesh_eval, tnt_eval, mesh_cull, tsdf_fusion, delaunay, simple_knn,
 train_epilogue): the signature declarations, the device seams (stream, device context, device check, current device, pointer) and the row
-validator.  The evaluation modules bind the seams to private names of their own (``_stream = gn.stream``): those names are what the
-host tests replace with stand-ins for the emulated library, and a module's workspaces are allocated through its own ``torch`` for
-the same reason (the tests put guard bytes behind them)."""
+validator.  The evaluation modules, tsdf_fusion and delaunay bind the seams to private names of their own (``_stream = gn.stream``):
+those names are what the host tests replace with stand-ins for the emulated library, and a module's workspaces are allocated
+through its own ``torch`` for the same reason (the tests put guard bytes behind them); tsdf_fusion allocates through its
+``_buffer``, by role."""
 import ctypes as C
 
 import torch

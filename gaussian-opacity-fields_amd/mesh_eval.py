@@ -48,6 +48,7 @@ def last_stats():
 
 
 # the device seams, by the names the host tests replace per module (tests/test_mesh_eval_host.py); one definition each: gof_native
+# (tsdf_fusion and delaunay bind them the same way)
 _stream, _device_of, _on_device, _ptr = gn.stream, gn.device_of, gn.on_device, gn.ptr
 _device = functools.partial(gn.current_device, "mesh_eval")
 

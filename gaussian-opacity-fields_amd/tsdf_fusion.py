@@ -14,6 +14,7 @@ There is no host fallback: every step runs on the device or raises.
 """
 import collections
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -64,6 +65,18 @@ def _dptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+# the device seams, by the names the host tests replace per module (tests/test_tsdf_host.py); one definition each: gof_native
+_stream, _device_of, _on_device = gn.stream, gn.device_of, gn.on_device
+_device = functools.partial(gn.current_device, "TSDFVolume")
+
+
+def _buffer(role, shape, dtype, device):
+    """Every device buffer of a TSDFVolume, by its role: the five arrays of GofTsdfVolume under their field names, "frame ws",
+    "extract ws", "block_coords" and the four fields of TriangleMesh.  The one seam of this module alone: the host tests decide here
+    what a buffer of each role holds when the library receives it."""
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
 class TSDFVolume:
     """Sparse TSDF volume of 16^3-voxel blocks on a ROCm device (DESIGN.md "TSDF fusion").
 
@@ -78,7 +91,7 @@ class TSDFVolume:
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("TSDFVolume (gfx950 backend) needs a ROCm device, got %s" % dev)
-        self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        self.device = dev if dev.index is not None else _device()
         self.voxel_size = float(voxel_size)
         self.trunc = float(trunc_voxel_multiplier) * self.voxel_size
         self._n = 0
@@ -91,14 +104,12 @@ class TSDFVolume:
     def _alloc(self, block_capacity):
         dev = self.device
         tcap = _pow2_at_least(2 * block_capacity)
-        bufs = dict(table_keys=torch.empty(tcap, dtype=torch.int64, device=dev), table_vals=torch.empty(tcap, dtype=torch.int32, device=dev),
-                    block_keys=torch.empty(block_capacity, dtype=torch.int64, device=dev),
-                    block_data=torch.empty(block_capacity * 5 * _VOXELS, dtype=torch.float32, device=dev),
-                    counter=torch.empty(4, dtype=torch.int32, device=dev))
-        vol = GofTsdfVolume(self.voxel_size, self.trunc, BLOCK_RESOLUTION, 0, tcap, block_capacity,
-                            *[bufs[k].data_ptr() for k in ("table_keys", "table_vals", "block_keys", "block_data", "counter")])
-        with torch.cuda.device(dev):
-            B._check(B.lib.gof_tsdf_grow(C.byref(vol), C.byref(self._vol) if self._vol is not None else None, self._n, B._stream()))
+        bufs = {role: _buffer(role, count, dtype, dev) for role, count, dtype in (
+            ("table_keys", tcap, torch.int64), ("table_vals", tcap, torch.int32), ("block_keys", block_capacity, torch.int64),
+            ("block_data", block_capacity * 5 * _VOXELS, torch.float32), ("counter", 4, torch.int32))}
+        vol = GofTsdfVolume(self.voxel_size, self.trunc, BLOCK_RESOLUTION, 0, tcap, block_capacity, *[b.data_ptr() for b in bufs.values()])
+        with _device_of(bufs["counter"]):
+            B._check(B.lib.gof_tsdf_grow(C.byref(vol), C.byref(self._vol) if self._vol is not None else None, self._n, _stream()))
         self._bufs, self._vol = bufs, vol         # (the old buffers are freed in stream order behind the copy)
 
     @property
@@ -111,10 +122,10 @@ class TSDFVolume:
 
     def block_coords(self):
         """[num_blocks, 3] int32 block coordinates, in storage order (the order of block_data())"""
-        out = torch.empty((self._n, 3), dtype=torch.int32, device=self.device)
+        out = _buffer("block_coords", (self._n, 3), torch.int32, self.device)
         if self._n:
-            with torch.cuda.device(self.device):
-                B._check(B.lib.gof_tsdf_block_coords(C.byref(self._vol), self._n, _dptr(out), B._stream()))
+            with _device_of(out):
+                B._check(B.lib.gof_tsdf_block_coords(C.byref(self._vol), self._n, _dptr(out), _stream()))
         return out
 
     def block_data(self):
@@ -125,7 +136,7 @@ class TSDFVolume:
     def _frame_workspace(self):
         need = int(B.lib.gof_tsdf_frame_ws_bytes(self._set_cap))
         if self._frame_ws is None or self._frame_ws.numel() < need:
-            self._frame_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._frame_ws = _buffer("frame ws", need, torch.uint8, self.device)
         return self._frame_ws
 
     def _camera(self, m, shape):
@@ -138,7 +149,7 @@ class TSDFVolume:
     def integrate(self, depth, color, intrinsic, extrinsic, depth_scale=1.0, depth_max=6.0):
         """depth [H,W] or [1,H,W], color [3,H,W] or [H,W,3] (device tensors); intrinsic 3x3 (fx, fy, cx, cy are used), extrinsic 4x4
         world->camera.  A pixel is valid iff 0 < depth / depth_scale <= depth_max."""
-        if depth.device.type != "cuda" or color.device.type != "cuda":
+        if not _on_device(depth) or not _on_device(color):
             raise RuntimeError("TSDFVolume.integrate needs device tensors")
         d = depth.detach()
         if d.dim() == 3 and d.shape[0] == 1:
@@ -158,8 +169,8 @@ class TSDFVolume:
         K = self._camera(intrinsic, (3, 3))
         E = self._camera(extrinsic, (4, 4))
         nf, nn = C.c_int64(0), C.c_int64(0)
-        with torch.cuda.device(self.device):
-            stream = B._stream()
+        with _device_of(d):
+            stream = _stream()
             while True:
                 ws = self._frame_workspace()
                 rc = B.lib.gof_tsdf_touch(C.byref(self._vol), _dptr(d), H, W, _dptr(K), _dptr(E), float(depth_scale), float(depth_max),
@@ -185,15 +196,15 @@ class TSDFVolume:
         dev = self.device
         n = self._n
         nv, nt = C.c_int64(0), C.c_int64(0)
-        with torch.cuda.device(dev):
-            stream = B._stream()
-            ws = torch.empty(int(B.lib.gof_tsdf_extract_ws_bytes(n)), dtype=torch.uint8, device=dev)
+        with _device_of(self._bufs["counter"]):
+            stream = _stream()
+            ws = _buffer("extract ws", int(B.lib.gof_tsdf_extract_ws_bytes(n)), torch.uint8, dev)
             B._check(B.lib.gof_tsdf_extract_count(C.byref(self._vol), n, float(weight_threshold), _dptr(ws), ws.numel(), C.byref(nv), C.byref(nt), stream))
             V, F = int(nv.value), int(nt.value)
-            verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
-            cols = torch.empty((V, 3), dtype=torch.float32, device=dev)
-            nrms = torch.empty((V, 3), dtype=torch.float32, device=dev)
-            tris = torch.empty((F, 3), dtype=torch.int32, device=dev)
+            verts = _buffer("vertices", (V, 3), torch.float32, dev)
+            cols = _buffer("colors", (V, 3), torch.float32, dev)
+            nrms = _buffer("normals", (V, 3), torch.float32, dev)
+            tris = _buffer("triangles", (F, 3), torch.int32, dev)
             if V or F:
                 B._check(B.lib.gof_tsdf_extract_emit(C.byref(self._vol), n, float(weight_threshold), _dptr(ws), ws.numel(), V, F,
                                                      _dptr(verts), _dptr(tris), _dptr(cols), _dptr(nrms), stream))

@@ -1,24 +1,24 @@
 """CPU tests of the Delaunay tetrahedralization: the kernels of csrc/delaunay.hip through the host emulator
-(tests/hipemu), each run in a child process so that an emulator abort fails one test, not the session, held to the independent
-checker (tests/delaunay_check.py) and, in general position, to SciPy's Qhull; plus the tetranerf shim's host path."""
-import ctypes as C
+(tests/hipemu) behind delaunay.triangulate itself, each run in a child process so that an emulator abort fails one test, not the
+session, held to the independent checker (tests/delaunay_check.py) and, in general position, to SciPy's Qhull; plus the tetranerf
+shim's host path.
+
+In the child the product module runs unchanged except for the test seams of tests/hipemu/host_child.py: GOF_HIP_LIB names the
+emulated library, the device check / stream / device context are host stand-ins, and every arena is filled with 0xA5 (as
+uninitialised as a device allocation) and followed by guard bytes that are checked after the run."""
+import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "gaussian-opacity-fields_amd")
-for _p in (HERE, PKG, os.path.join(HERE, "hipemu")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hipemu"))
+import host_child  # noqa: E402
+from host_child import PKG  # noqa: E402
 import delaunay_check as K  # noqa: E402
 
-GOF_E_INVALID, GOF_E_CAPACITY = -1, -5
+GOF_E_INVALID = -1
 
 
 def case_points(name):
@@ -66,65 +66,25 @@ def case_points(name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the emulated library, driven from a child process
+# the child: delaunay.triangulate over the emulated library
 # ---------------------------------------------------------------------------------------------------------------------------
-def _emu_lib():
-    import build_emu
-    lib = C.CDLL(build_emu.build())
-    lib.gof_last_error.restype = C.c_char_p
-    lib.gof_delaunay_ws_bytes.restype = C.c_size_t
-    lib.gof_delaunay_ws_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.gof_delaunay_build.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]
-    lib.gof_delaunay_emit.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.gof_delaunay_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    return lib
-
-
-def emu_triangulate(lib, P, cap=None):
-    """triangulate's host logic over numpy buffers -> (rc, cells, stats, retries)"""
-    P = np.ascontiguousarray(P, np.float32)
-    n = len(P)
-    cap = cap or 7 * n + 64
-    retries = 0
-    while True:
-        ws = np.full(lib.gof_delaunay_ws_bytes(n, cap) + 256, 0xA5, np.uint8)      # (as uninitialised as a device allocation)
-        m = C.c_int64()
-        rc = lib.gof_delaunay_build(n, P.ctypes.data if n else None, cap, ws.ctypes.data, ws.size, C.byref(m), None)
-        if rc == GOF_E_CAPACITY and m.value > cap:
-            cap, retries = m.value, retries + 1
-            continue
-        if rc:
-            return rc, np.zeros((0, 4), np.int32), np.zeros(8, np.int64), retries
-        break
-    T = np.zeros((m.value, 4), np.int32)
-    assert lib.gof_delaunay_emit(ws.ctypes.data, m.value, T.ctypes.data, None) == 0, lib.gof_last_error()
-    st = np.zeros(8, np.int64)
-    assert lib.gof_delaunay_stats(ws.ctypes.data, st.ctypes.data, None) == 0
-    return rc, T, st, retries
-
-
 def _child(name, out, cap):
-    lib = _emu_lib()
-    base = name.split("@")[0]
-    rc, T, st, retries = emu_triangulate(lib, case_points(base), cap=cap)
-    np.savez(out, rc=rc, T=T, stats=st, retries=retries)
+    import torch
+    import delaunay
+    check = host_child.install_seams(delaunay)
+    res = {"T": np.zeros((0, 4), np.int32), "code": 0, "error": ""}
+    try:
+        res["T"] = delaunay.triangulate(torch.from_numpy(case_points(name)), capacity=cap or None).numpy()
+    except RuntimeError as e:
+        res["code"], res["error"] = getattr(e, "code", 0), str(e)
+    assert check() > 0
+    np.savez(out, stats=json.dumps(delaunay.last_stats()), **res)
 
 
 def _emulate(name, tmp_path, order=None, cap=0):
-    out = str(tmp_path / ("%s_%s_%d.npz" % (name, (order or "forward").replace(":", "_"), cap)))
-    env = dict(os.environ)
-    if order:
-        env["HIPEMU_ORDER"] = order
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), name, out, str(cap)], env=env, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, "emulated run of %s (order %s) failed (rc %d):\n%s\n%s" % (name, order, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    res = dict(np.load(out))
-    return int(res["rc"]), res["T"], res["stats"], int(res["retries"])
-
-
-def _needs_emulator():
-    import build_emu
-    if not os.path.exists(build_emu.CXX):
-        pytest.skip("no host clang++ (%s) to build the emulated library" % build_emu.CXX)
+    """-> (None or the (code, text) of the error triangulate raised, cells, last_stats())"""
+    res = host_child.run_child(__file__, name, tmp_path, cap, order=order, timeout=1200)
+    return (int(res["code"]), str(res["error"])) if str(res["error"]) else None, res["T"], json.loads(str(res["stats"]))
 
 
 def _scipy_sets(P):
@@ -135,34 +95,31 @@ def _scipy_sets(P):
 # ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["uniform_2k", "uniform_20k"])
 def test_uniform_matches_scipy(name, tmp_path):
-    _needs_emulator()
-    rc, T, st, _ = _emulate(name, tmp_path)
-    assert rc == 0
+    err, T, st = _emulate(name, tmp_path)
+    assert err is None
     P = case_points(name)
     K.check(P, T)
     assert K.as_sets(T) == _scipy_sets(P)
-    assert st[0] > 0 and st[5] == len(P)
+    assert st["rounds"] > 0 and st["distinct_points"] == len(P)
 
 
 @pytest.mark.parametrize("name", ["tetra_2k", "lattice", "sphere", "scales"])
 def test_degenerate_inputs_are_valid(name, tmp_path):
-    _needs_emulator()
-    rc, T, st, _ = _emulate(name, tmp_path)
-    assert rc == 0
+    err, T, st = _emulate(name, tmp_path)
+    assert err is None
     P = case_points(name)
     info = K.check(P, T, hull_sample=4000)
     if name == "lattice":
-        assert st[1] > 0, "the lattice must reach the exact predicates"
+        assert st["exact_evaluations"] > 0, "the lattice must reach the exact predicates"
         assert len(T) >= 7 ** 3 * 5
     if name == "sphere":
-        assert st[3] > 0, "the centre of a sphere needs a cavity beyond the fast path's slot"
+        assert st["slow_insertions"] > 0, "the centre of a sphere needs a cavity beyond the fast path's slot"
         assert info["boundary_faces"] > 0
 
 
 def test_duplicates_keep_the_lowest_index(tmp_path):
-    _needs_emulator()
-    rc, T, _, _ = _emulate("dup", tmp_path)
-    assert rc == 0
+    err, T, _ = _emulate("dup", tmp_path)
+    assert err is None
     P = case_points("dup")
     K.check(P, T)                       # (all distinct points used, by their lowest-index copy)
     rep = K.representatives(P)
@@ -171,20 +128,17 @@ def test_duplicates_keep_the_lowest_index(tmp_path):
 
 @pytest.mark.parametrize("name", ["coplanar", "three", "dup4"])
 def test_degenerate_dimension_gives_no_cells(name, tmp_path):
-    _needs_emulator()
-    rc, T, _, _ = _emulate(name, tmp_path)
-    assert rc == 0 and T.shape == (0, 4)
+    err, T, _ = _emulate(name, tmp_path)
+    assert err is None and T.shape == (0, 4)
 
 
 def test_non_finite_input_is_invalid(tmp_path):
-    _needs_emulator()
-    rc, T, _, _ = _emulate("nan", tmp_path)
-    assert rc == GOF_E_INVALID
+    err, T, _ = _emulate("nan", tmp_path)
+    assert err is not None and err[0] == GOF_E_INVALID
 
 
 def test_canonical_form(tmp_path):
-    _needs_emulator()
-    rc, T, _, _ = _emulate("uniform_2k", tmp_path)
+    _, T, _ = _emulate("uniform_2k", tmp_path)
     T = T.astype(np.int64)
     assert (T[:, 0] < T[:, 1:].min(1)).all() and (T[:, 1] < T[:, 2:].min(1)).all()
     order = np.lexsort((T[:, 3], T[:, 2], T[:, 1], T[:, 0]))
@@ -193,25 +147,22 @@ def test_canonical_form(tmp_path):
 
 @pytest.mark.parametrize("order", ["reverse", "random:5"])
 def test_bytes_do_not_depend_on_the_schedule(order, tmp_path):
-    _needs_emulator()
-    _, T0, _, _ = _emulate("lattice", tmp_path)
-    _, T1, _, _ = _emulate("lattice", tmp_path, order=order)
+    _, T0, _ = _emulate("lattice", tmp_path)
+    _, T1, _ = _emulate("lattice", tmp_path, order=order)
     assert T0.tobytes() == T1.tobytes()
 
 
 def test_permuted_input_gives_permuted_cells(tmp_path):
-    _needs_emulator()
-    _, T0, _, _ = _emulate("lattice", tmp_path)
-    _, T1, _, _ = _emulate("lattice_perm", tmp_path)
+    _, T0, _ = _emulate("lattice", tmp_path)
+    _, T1, _ = _emulate("lattice_perm", tmp_path)
     perm = np.random.default_rng(11).permutation(512)
     assert K.as_sets(perm[T1]) == K.as_sets(T0)
 
 
 def test_tiny_capacity_retries_to_the_same_bytes(tmp_path):
-    _needs_emulator()
-    _, T0, _, r0 = _emulate("uniform_2k", tmp_path)
-    _, T1, _, r1 = _emulate("uniform_2k", tmp_path, cap=64)
-    assert r0 == 0 and r1 > 0
+    _, T0, s0 = _emulate("uniform_2k", tmp_path)
+    _, T1, s1 = _emulate("uniform_2k", tmp_path, cap=64)
+    assert s0["retries"] == 0 and s1["retries"] > 0
     assert T0.tobytes() == T1.tobytes()
 
 

@@ -14,17 +14,13 @@ second coefficient, the largest-query case, and that the reference finds no thir
 import ctypes as C
 import functools
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, os.path.join(HERE, "hipemu")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hipemu"))
+import host_child  # noqa: E402
 import delaunay_exact as X  # noqa: E402
 import delaunay_predicate_cases as G  # noqa: E402
 
@@ -128,8 +124,7 @@ def check_class(name, res):
 # the emulated library, driven from a child process
 # ---------------------------------------------------------------------------------------------------------------------------
 def _emu_lib():
-    import build_emu
-    lib = C.CDLL(build_emu.build())
+    lib = C.CDLL(os.environ["GOF_HIP_LIB"])
     lib.gof_last_error.restype = C.c_char_p
     lib.gof_debug_delaunay_predicates.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
@@ -172,13 +167,7 @@ def _child(name, out):
 
 
 def _emulate(name, tmp_path):
-    import build_emu
-    if not os.path.exists(build_emu.CXX):
-        pytest.skip("no host clang++ (%s) to build the emulated library" % build_emu.CXX)
-    out = str(tmp_path / (name + ".npz"))
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), name, out], capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, "emulated run of %s failed (rc %d):\n%s\n%s" % (name, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    return dict(np.load(out))
+    return host_child.run_child(__file__, name, tmp_path, timeout=1200)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

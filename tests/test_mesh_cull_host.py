@@ -8,23 +8,18 @@ stream / device context are replaced by host stand-ins, and EVERY buffer mesh_cu
 read must have been written by them."""
 import ast
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "gaussian-opacity-fields_amd")
-for _p in (HERE, PKG, os.path.join(HERE, "hipemu")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
+sys.path.insert(0, os.path.join(HERE, "hipemu"))
+import host_child  # noqa: E402
+from host_child import PKG  # noqa: E402
 import mesh_cull_cases as K  # noqa: E402
 import mesh_cull_restatement as R  # noqa: E402
 
-GUARD = 256
 GOLDEN = os.path.join(HERE, "golden", "ref_dtu_cull_golden.npz")
 REF_SCRIPT = "/root/reference/evaluate_dtu_mesh.py"
 
@@ -36,37 +31,6 @@ def golden():
 # ---------------------------------------------------------------------------------------------------------------------------
 # the child: mesh_cull over the emulated library
 # ---------------------------------------------------------------------------------------------------------------------------
-def _host_mesh_cull():
-    """mesh_cull with the test seams (see the module docstring) -> (module, check_guards)"""
-    import contextlib
-    import torch
-    import mesh_cull
-    held = []
-
-    class TorchWithGuards:
-        def __getattr__(self, k):
-            return getattr(torch, k)
-
-        @staticmethod
-        def empty(shape, dtype=None, device=None):
-            shape = (shape,) if isinstance(shape, int) else tuple(int(s) for s in shape)
-            nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
-            buf = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8)
-            held.append((buf, nbytes))
-            return buf[:nbytes].view(dtype).reshape(shape)
-
-    def check():
-        for buf, n in held:
-            assert (buf[n:] == 0xA5).all(), "guard bytes behind a %d-byte buffer were overwritten" % n
-        return len(held)
-    mesh_cull.torch = TorchWithGuards()
-    mesh_cull._on_device = lambda t: True
-    mesh_cull._stream = lambda: None
-    mesh_cull._device_of = lambda t: contextlib.nullcontext()
-    mesh_cull._device = lambda: torch.device("cpu")
-    return mesh_cull, check
-
-
 def _up(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a))
@@ -81,7 +45,8 @@ def _cameras(g):
 
 
 def _child(case, out):
-    M, check = _host_mesh_cull()
+    import mesh_cull as M
+    check = host_child.install_seams(M, buffers="all")
     kind, name = case.split(":", 1)
     if kind == "dilate":
         res = K.run_dilate(M, _up, tuple(int(v) for v in name.split("x")))
@@ -159,19 +124,8 @@ def _child(case, out):
     np.savez(out, **res)
 
 
-def _needs_emulator():
-    import build_emu
-    if not os.path.exists(build_emu.CXX):
-        pytest.skip("no host clang++ (%s) to build the emulated library" % build_emu.CXX)
-    return build_emu.build()
-
-
 def _emulate(case, tmp_path):
-    lib = _needs_emulator()
-    out = str(tmp_path / ("%s.npz" % case.replace(":", "_")))
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), case, out], env=dict(os.environ, GOF_HIP_LIB=lib), capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, "emulated run of %s failed (rc %d):\n%s\n%s" % (case, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    res = dict(np.load(out))
+    res = host_child.run_child(__file__, case, tmp_path, timeout=1800)
     assert int(res["buffers"]) > 0
     return res
 

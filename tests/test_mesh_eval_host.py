@@ -2,27 +2,20 @@
 (tests/hipemu) behind mesh_eval's own Python layer, each run in a child process (an emulator abort fails one test, not the
 session), held to tests/mesh_eval_restatement.py with equalities: sample coordinates, keep masks and nearest distances bit for bit.
 
-In the child the product module runs unchanged except for three test seams: GOF_HIP_LIB names the emulated library, the device
-check / stream / device context are replaced by host stand-ins, and every workspace mesh_eval allocates is filled with 0xA5 and
-followed by guard bytes that are checked after the run.  Sizes stay at or below 50 k points per case."""
+In the child the product module runs unchanged except for three test seams (tests/hipemu/host_child.py): GOF_HIP_LIB names the
+emulated library, the device check / stream / device context are replaced by host stand-ins, and every workspace mesh_eval
+allocates is filled with 0xA5 and followed by guard bytes that are checked after the run.  Sizes stay at or below 50 k points per case."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "gaussian-opacity-fields_amd")
-for _p in (HERE, PKG, os.path.join(HERE, "hipemu")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hipemu"))
+import host_child  # noqa: E402
+from host_child import PKG  # noqa: E402
 import mesh_eval_restatement as R  # noqa: E402
-
-GUARD = 256
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -165,41 +158,10 @@ def write_scan(root, scan=7):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the child: mesh_eval over the emulated library
 # ---------------------------------------------------------------------------------------------------------------------------
-def _host_mesh_eval():
-    """mesh_eval with the three test seams (see the module docstring) -> (module, check_guards)"""
-    import contextlib
-    import torch
-    import mesh_eval
-    held = []
-
-    class TorchWithGuards:
-        def __getattr__(self, k):
-            return getattr(torch, k)
-
-        @staticmethod
-        def empty(*a, **k):
-            if k.get("dtype") is torch.uint8 and len(a) == 1 and isinstance(a[0], int):
-                buf = torch.full((a[0] + GUARD,), 0xA5, dtype=torch.uint8)
-                held.append((buf, a[0]))
-                return buf[:a[0]]
-            k.pop("device", None)
-            return torch.empty(*a, **k)
-
-    def check():
-        for buf, n in held:
-            assert (buf[n:] == 0xA5).all(), "guard bytes behind a %d-byte workspace were overwritten" % n
-        return len(held)
-    mesh_eval.torch = TorchWithGuards()
-    mesh_eval._on_device = lambda t: True
-    mesh_eval._stream = lambda: None
-    mesh_eval._device_of = lambda t: contextlib.nullcontext()
-    mesh_eval._device = lambda: torch.device("cpu")
-    return mesh_eval, check
-
-
 def _child(case, out):
     import torch
-    M, check = _host_mesh_eval()
+    import mesh_eval as M
+    check = host_child.install_seams(M)
     kind, name = case.split(":", 1)
     res = {}
     tt = torch.from_numpy
@@ -247,22 +209,8 @@ def _child(case, out):
     np.savez(out, **res)
 
 
-def _needs_emulator():
-    import build_emu
-    if not os.path.exists(build_emu.CXX):
-        pytest.skip("no host clang++ (%s) to build the emulated library" % build_emu.CXX)
-    return build_emu.build()
-
-
 def _emulate(case, tmp_path, order=None):
-    lib = _needs_emulator()
-    out = str(tmp_path / ("%s_%s.npz" % (case.replace(":", "_"), (order or "forward").replace(":", "_"))))
-    env = dict(os.environ, GOF_HIP_LIB=lib)
-    if order:
-        env["HIPEMU_ORDER"] = order
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), case, out], env=env, capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, "emulated run of %s (order %s) failed (rc %d):\n%s\n%s" % (case, order, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    res = dict(np.load(out))
+    res = host_child.run_child(__file__, case, tmp_path, order=order, timeout=1800)
     assert int(res["workspaces"]) > 0 or case.startswith("cli")
     return res
 

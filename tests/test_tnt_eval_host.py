@@ -8,22 +8,16 @@ emulated library, the device check / stream / device context are replaced by hos
 0xA5 and followed by guard bytes that are checked after the run.  Sizes stay at or below 50 k points per case."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "gaussian-opacity-fields_amd")
-for _p in (HERE, PKG, os.path.join(HERE, "hipemu")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hipemu"))
+import host_child  # noqa: E402
+from host_child import PKG  # noqa: E402
 import tnt_eval_restatement as R  # noqa: E402
 
-GUARD = 256
 TAU = 0.5
 
 
@@ -233,40 +227,6 @@ def restated_run(sc, seed):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the child: tnt_eval over the emulated library
 # ---------------------------------------------------------------------------------------------------------------------------
-def _host_tnt_eval():
-    """tnt_eval (and the mesh_eval it calls) with the test seams -> (module, check_guards)"""
-    import contextlib
-    import torch
-    import mesh_eval
-    import tnt_eval
-    held = []
-
-    class TorchWithGuards:
-        def __getattr__(self, k):
-            return getattr(torch, k)
-
-        @staticmethod
-        def empty(*a, **k):
-            if k.get("dtype") is torch.uint8 and len(a) == 1 and isinstance(a[0], int):
-                buf = torch.full((a[0] + GUARD,), 0xA5, dtype=torch.uint8)
-                held.append((buf, a[0]))
-                return buf[:a[0]]
-            k.pop("device", None)
-            return torch.empty(*a, **k)
-
-    def check():
-        for buf, n in held:
-            assert (buf[n:] == 0xA5).all(), "guard bytes behind a %d-byte workspace were overwritten" % n
-        return len(held)
-    for mod in (mesh_eval, tnt_eval):
-        mod.torch = TorchWithGuards()
-        mod._on_device = lambda t: True
-        mod._stream = lambda: None
-        mod._device_of = lambda t: contextlib.nullcontext()
-        mod._device = lambda: torch.device("cpu")
-    return tnt_eval, check
-
-
 def pack_record(record):
     """the per-evaluation record as arrays (a missing sums2 is NaN)"""
     return {"rec_T": np.array([e["transformation"] for e in record]).reshape(-1, 4, 4), "rec_n": np.array([e["n"] for e in record], np.int64),
@@ -354,28 +314,16 @@ def run_case(M, case, workdir, tt):
 
 def _child(case, out):
     import torch
-    M, check = _host_tnt_eval()
+    import mesh_eval
+    import tnt_eval as M
+    check = host_child.install_seams(mesh_eval, M)          # (tnt_eval and the mesh_eval it calls)
     res = run_case(M, case, os.path.dirname(out), lambda a: torch.from_numpy(np.ascontiguousarray(a)))
     res["workspaces"] = np.array(check())
     np.savez(out, **res)
 
 
-def _needs_emulator():
-    import build_emu
-    if not os.path.exists(build_emu.CXX):
-        pytest.skip("no host clang++ (%s) to build the emulated library" % build_emu.CXX)
-    return build_emu.build()
-
-
 def _emulate(case, tmp_path, order=None):
-    lib = _needs_emulator()
-    out = str(tmp_path / ("%s_%s.npz" % (case.replace(":", "_"), (order or "forward").replace(":", "_"))))
-    env = dict(os.environ, GOF_HIP_LIB=lib)
-    if order:
-        env["HIPEMU_ORDER"] = order
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), case, out], env=env, capture_output=True, text=True, timeout=3000)
-    assert r.returncode == 0, "emulated run of %s (order %s) failed (rc %d):\n%s\n%s" % (case, order, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    res = dict(np.load(out))
+    res = host_child.run_child(__file__, case, tmp_path, order=order, timeout=3000)
     assert int(res["workspaces"]) > 0
     return res
 

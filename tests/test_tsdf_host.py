@@ -1,8 +1,11 @@
 """CPU tests of the TSDF fusion (DESIGN.md "TSDF fusion"): the kernels of csrc/tsdf.hip through the host emulator (tests/hipemu)
-against the float64 restatement (tests/tsdf_restatement.py), the PLY writer, the marching-cubes tables, and the launcher's binding of
-extract_mesh_tsdf.py's tsdf_fusion."""
+behind tsdf_fusion.TSDFVolume itself, against the float64 restatement (tests/tsdf_restatement.py), the PLY writer, the marching-cubes
+tables, and the launcher's binding of extract_mesh_tsdf.py's tsdf_fusion.
+
+In the child the product module runs unchanged except for its test seams: GOF_HIP_LIB names the emulated library, the device check /
+stream / device context are the host stand-ins of tests/hipemu/host_child.py, and tsdf_fusion._buffer, through which a TSDFVolume
+allocates every buffer by role, applies the fill policy below."""
 import ast
-import ctypes as C
 import inspect
 import os
 import subprocess
@@ -11,13 +14,9 @@ import sys
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "gaussian-opacity-fields_amd")
-for _p in (HERE, PKG, os.path.join(HERE, "hipemu")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hipemu"))
+import host_child  # noqa: E402
+from host_child import PKG  # noqa: E402
 import tsdf_restatement as T  # noqa: E402
 
 REF_SCRIPT = "/root/reference/extract_mesh_tsdf.py"
@@ -30,38 +29,10 @@ TAU = 1.0
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the emulated library, driven from a child process (an emulator abort fails one test, not the session)
+# the child: tsdf_fusion.TSDFVolume over the emulated library
 # ---------------------------------------------------------------------------------------------------------------------------
-class Vol(C.Structure):
-    _fields_ = [("voxel_size", C.c_float), ("trunc", C.c_float), ("block_resolution", C.c_int32), ("reserved0", C.c_int32),
-                ("table_capacity", C.c_int64), ("block_capacity", C.c_int64),
-                ("table_keys", C.c_void_p), ("table_vals", C.c_void_p), ("block_keys", C.c_void_p), ("block_data", C.c_void_p),
-                ("counter", C.c_void_p)]
-
-
-def _emu_lib():
-    import build_emu
-    lib = C.CDLL(build_emu.build())
-    vp, sz, i32, i64, f32 = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_float
-    V, P = C.POINTER(Vol), C.POINTER(i64)
-    lib.gof_last_error.restype = C.c_char_p
-    lib.gof_tsdf_frame_ws_bytes.restype = lib.gof_tsdf_extract_ws_bytes.restype = sz
-    lib.gof_tsdf_frame_ws_bytes.argtypes = lib.gof_tsdf_extract_ws_bytes.argtypes = [i64]
-    lib.gof_tsdf_grow.argtypes = [V, V, i64, vp]
-    lib.gof_tsdf_touch.argtypes = [V, vp, i32, i32, vp, vp, f32, f32, vp, sz, i64, P, P, vp]
-    lib.gof_tsdf_integrate.argtypes = [V, i64, vp, vp, i32, i32, vp, vp, f32, f32, vp, sz, i64, i64, i64, vp]
-    lib.gof_tsdf_extract_count.argtypes = [V, i64, f32, vp, sz, P, P, vp]
-    lib.gof_tsdf_extract_emit.argtypes = [V, i64, f32, vp, sz, i64, i64, vp, vp, vp, vp, vp]
-    lib.gof_tsdf_block_coords.argtypes = [V, i64, vp, vp]
-    return lib
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
-
-
 # ---- what a buffer holds when the library receives it (include/gof_hip.h: "workspaces may hold anything on entry unless stated") ------
-# the product's TSDFVolume allocates the volume's arrays and both workspaces with torch.empty: recycled memory.  GOF_TSDF_FILL (read by
+# TSDFVolume allocates the volume's arrays and both workspaces with torch.empty: recycled memory.  GOF_TSDF_FILL (read by
 # the child process) is "zero" (the default), "0xA5", "0xFF" (all-ones keys, counts and cursors, NaN voxels) or "stale": every buffer
 # holds what the buffer of the same role held when a LARGER volume (STALE_DONOR: more views, finer voxels, hence more blocks, a larger
 # table and larger frame sets) had been fused and extracted -- cut to the new size, or extended with 0xA5
@@ -72,87 +43,37 @@ _left = {}             # role -> the bytes the donor volume's last buffer of tha
 _recording = False
 
 
-def _buf(role, count, dtype):
-    """a workspace or volume array under the fill policy"""
-    a = np.empty(int(count), dtype)
-    raw = a.view(np.uint8)
-    if _fill == "zero":
-        raw[:] = 0
-    elif _fill == "0xFF":
+WRITTEN = ("block_coords", "vertices", "triangles", "colors", "normals")      # outputs the header documents as fully written
+
+
+def _buf(role, shape, dtype, device):
+    """tsdf_fusion._buffer on the host: a workspace or volume array under the fill policy; a fully written output as NaN / 0x7fffffff
+    under a poison policy (zero otherwise)"""
+    import torch
+    a = torch.zeros(shape, dtype=dtype)
+    if role in WRITTEN:
+        return a if _fill == "zero" else a.fill_(float("nan") if a.is_floating_point() else 0x7fffffff)
+    raw = a.view(torch.uint8)
+    if _fill == "0xFF":
         raw[:] = 0xFF
-    else:
+    elif _fill != "zero":
         raw[:] = 0xA5
         if _fill == "stale" and role in _left:
-            n = min(raw.size, _left[role].size)
-            raw[:n] = _left[role].view(np.uint8)[:n]
+            n = min(raw.numel(), _left[role].numel())
+            raw[:n] = _left[role].view(torch.uint8)[:n]
     if _recording:
-        _left[role] = a          # (the live array: what it holds when the donor is done)
+        _left[role] = a          # (the live tensor: what it holds when the donor is done)
     return a
 
 
-def _written(shape, dtype):
-    """an output the header documents as fully written: NaN / 0x7fffffff under a poison policy (zero as before otherwise)"""
-    a = np.zeros(shape, dtype)
-    if _fill != "zero":
-        a.fill(np.nan if a.dtype.kind == "f" else 0x7fffffff)
-    return a
-
-
-class EmuVolume:
-    """TSDFVolume's host logic over numpy buffers and the emulated library (growth included: it starts at 4 blocks)"""
-
-    def __init__(self, lib, v, block_count=4, set_cap=64):
-        self.lib, self.v, self.n, self.S = lib, v, 0, set_cap
-        self.keep = None
-        self.vol = None
-        self._alloc(block_count)
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError("gof_tsdf: %d %s" % (rc, self.lib.gof_last_error().decode()))
-
-    def _alloc(self, cap):
-        tcap = 1 << (2 * cap - 1).bit_length()
-        keep = [_buf("table_keys", tcap, np.uint64), _buf("table_vals", tcap, np.uint32), _buf("block_keys", cap, np.uint64),
-                _buf("block_data", cap * 5 * 4096, np.float32), _buf("counter", 4, np.uint32)]
-        vol = Vol(self.v, 8.0 * self.v, 16, 0, tcap, cap, *[a.ctypes.data for a in keep])
-        self._check(self.lib.gof_tsdf_grow(C.byref(vol), C.byref(self.vol) if self.vol is not None else None, self.n, None))
-        self.keep, self.vol = keep, vol
-
-    def integrate(self, depth, color_hw3, K, E):
-        d = np.ascontiguousarray(depth, np.float32)
-        c = np.ascontiguousarray(np.transpose(color_hw3, (2, 0, 1)), np.float32)
-        K32, E32 = np.ascontiguousarray(K, np.float32), np.ascontiguousarray(E, np.float32)
-        H, W = d.shape
-        nf, nn = C.c_int64(), C.c_int64()
-        while True:
-            ws = _buf("frame ws", self.lib.gof_tsdf_frame_ws_bytes(self.S), np.uint8)
-            rc = self.lib.gof_tsdf_touch(C.byref(self.vol), _p(d), H, W, _p(K32), _p(E32), 1.0, 6.0, _p(ws), ws.size, self.S, C.byref(nf), C.byref(nn), None)
-            if rc != -5:
-                self._check(rc)
-                break
-            self.S *= 2
-        if self.n + nn.value > self.vol.block_capacity:
-            self._alloc(max(2 * self.vol.block_capacity, self.n + nn.value))
-        self._check(self.lib.gof_tsdf_integrate(C.byref(self.vol), self.n, _p(d), _p(c), H, W, _p(K32), _p(E32), 1.0, 6.0, _p(ws), ws.size,
-                                                self.S, nf.value, nn.value, None))
-        self.n += nn.value
-        return nf.value, nn.value
-
-    def blocks(self):
-        """-> (coords [n,3] int32, data [n,5,16,16,16]) in storage order"""
-        co = _written((self.n, 3), np.int32)
-        self._check(self.lib.gof_tsdf_block_coords(C.byref(self.vol), self.n, _p(co), None))
-        return co, self.keep[3][:self.n * 5 * 4096].reshape(self.n, 5, 16, 16, 16).copy()
-
-    def extract(self, tau):
-        ws = _buf("extract ws", self.lib.gof_tsdf_extract_ws_bytes(self.n), np.uint8)
-        nv, nt = C.c_int64(), C.c_int64()
-        self._check(self.lib.gof_tsdf_extract_count(C.byref(self.vol), self.n, tau, _p(ws), ws.size, C.byref(nv), C.byref(nt), None))
-        V, F = nv.value, nt.value
-        out = [_written((V, 3), np.float32), _written((F, 3), np.int32), _written((V, 3), np.float32), _written((V, 3), np.float32)]
-        self._check(self.lib.gof_tsdf_extract_emit(C.byref(self.vol), self.n, tau, _p(ws), ws.size, V, F, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), None))
-        return out
+def _fuse(F, views, v, block_count=4):
+    """a TSDFVolume of `views` that starts small enough to grow its blocks and to redo a frame whose block set did not fit"""
+    vol = F.TSDFVolume(v, block_count=block_count)
+    vol._set_cap = 64
+    for d, c, K, E in views:
+        vol._frame_ws = None          # every frame workspace a fresh buffer under the fill policy
+        vol.integrate(F.torch.from_numpy(d), F.torch.from_numpy(np.ascontiguousarray(c)), K, E)
+    return vol
 
 
 def scene_inputs(name, voxel=None):
@@ -169,48 +90,40 @@ def scene_inputs(name, voxel=None):
 def run_emulated(name, out):
     """child process: every frame's block set (a one-frame volume each), the fused volume and its mesh -> npz"""
     global _fill, _recording
-    lib = _emu_lib()
+    import tsdf_fusion as F
+    host_child.install_seams(F, buffers=None)
+    F._buffer = _buf
+    touch, redone = F.B.lib.gof_tsdf_touch, []
+
+    def counted_touch(*args):          # (a frame redone with twice the slots: the touch returns GOF_E_CAPACITY)
+        rc = touch(*args)
+        redone.append(rc == -5)
+        return rc
+    F.B.lib.gof_tsdf_touch = counted_touch
     _fill = os.environ.get("GOF_TSDF_FILL", "zero")
     assert _fill in FILLS, _fill
     if _fill == "stale":          # the larger volume first: fused and extracted on 0xA5 buffers, which then are what it left behind
         _fill, _recording = "0xA5", True
-        dviews, dv = scene_inputs(*STALE_DONOR)
-        donor = EmuVolume(lib, dv)
-        for d, c, K, E in dviews:
-            donor.integrate(d, c, K, E)
-        donor.extract(TAU)
-        _left.update({k: a.copy() for k, a in _left.items()})
+        donor = _fuse(F, *scene_inputs(*STALE_DONOR))
+        donor.extract_triangle_mesh(TAU)
+        _left.update({k: a.clone() for k, a in _left.items()})
         _fill, _recording = "stale", False
     views, v = scene_inputs(name)
     res = {}
-    for i, (d, c, K, E) in enumerate(views):
-        one = EmuVolume(lib, v, block_count=1)
-        one.integrate(d, c, K, E)
-        res["frame%d" % i] = one.blocks()[0]
-    vol = EmuVolume(lib, v)
-    for d, c, K, E in views:
-        vol.integrate(d, c, K, E)
-    res["coords"], res["data"] = vol.blocks()
-    res["V"], res["F"], res["C"], res["N"] = vol.extract(TAU)
+    for i, view in enumerate(views):
+        res["frame%d" % i] = _fuse(F, [view], v, block_count=1).block_coords().numpy()
+    vol = _fuse(F, views, v)
+    assert vol.block_capacity > 4 and vol._set_cap > 64, "the scene no longer reaches the block growth and the redone frame"
+    assert any(redone) or name != "boxes", "no frame of boxes (the scene whose frame sets exceed 64 slots) was redone"
+    res["coords"], res["data"] = vol.block_coords().numpy(), vol.block_data().numpy().copy()
+    res["V"], res["F"], res["C"], res["N"] = (t.numpy() for t in vol.extract_triangle_mesh(TAU))
     if _fill == "stale":
-        assert donor.n > vol.n and donor.vol.table_capacity >= vol.vol.table_capacity, "the stale policy's donor volume is not the larger one"
+        assert donor.num_blocks > vol.num_blocks and donor._vol.table_capacity >= vol._vol.table_capacity, "the stale policy's donor volume is not the larger one"
     np.savez(out, **res)
 
 
 def _emulate(name, tmp_path, order=None, fill="zero"):
-    out = str(tmp_path / ("%s_%s_%s.npz" % (name, (order or "forward").replace(":", "_"), fill)))
-    env = dict(os.environ, GOF_TSDF_FILL=fill)
-    if order:
-        env["HIPEMU_ORDER"] = order
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), name, out], env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, "emulated run of %s (order %s) failed (rc %d):\n%s\n%s" % (name, order, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
-    return dict(np.load(out))
-
-
-def _needs_emulator():
-    import build_emu
-    if not os.path.exists(build_emu.CXX):
-        pytest.skip("no host clang++ (%s) to build the emulated library" % build_emu.CXX)
+    return host_child.run_child(__file__, name, tmp_path, order=order, env={"GOF_TSDF_FILL": fill}, tag=fill, timeout=900)
 
 
 def check_against_restatement(name, res):
@@ -258,7 +171,6 @@ def check_against_restatement(name, res):
 
 @pytest.mark.parametrize("name", sorted(EMU_SCENES))
 def test_emulated_kernels_match_restatement(name, tmp_path):
-    _needs_emulator()
     check_against_restatement(name, _emulate(name, tmp_path))
 
 
@@ -270,7 +182,6 @@ _zero_filled = {}
 def test_emulated_kernels_do_not_depend_on_what_their_buffers_held(name, fill, tmp_path):
     """the volume's arrays (gof_tsdf_grow's destination), the frame and the extract workspace filled with 0xA5, with 0xFF, or left over
     from a larger volume: the same comparison with the restatement, and every bit of the run on cleared buffers (blocks in key order)"""
-    _needs_emulator()
     got = _emulate(name, tmp_path, fill=fill)
     check_against_restatement(name, got)
     if name not in _zero_filled:
@@ -290,7 +201,6 @@ def test_emulated_kernels_do_not_depend_on_what_their_buffers_held(name, fill, t
 @pytest.mark.parametrize("order", ["reverse", "random:7"])
 def test_emulated_kernels_independent_of_lane_order(order, tmp_path):
     """the mesh is bit-identical, and the volume (in key order) equal, whatever order the emulator runs lanes and waves in"""
-    _needs_emulator()
     a = _emulate("sphere", tmp_path)
     b = _emulate("sphere", tmp_path, order)
     for k in ("V", "F", "C", "N"):
