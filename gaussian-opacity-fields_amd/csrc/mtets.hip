@@ -18,8 +18,12 @@
 //           the triangle table at its scanned position (1-triangle tets first, then 2-triangle tets,
 //           per 32 Mi-tet chunk: the order tetmesh.py:126-136 / :55-95 produces).
 //
-// Indices at the boundary are int64 (the reference's dtype); vertex ids must be < 2^32 and 6 * #tets < 2^32 (the scans and the
-// sort count in 32 bits).  Scan and sort are the hand-written kernels of radix.hip -- no library primitives.
+// Indices at the boundary are int64 (the reference's dtype); #vertices must be < 2^32 and 6 * #tets < 2^32 (the scans and the
+// sort count in 32 bits).  Every vertex id of every tet must lie in [0, V): mt_classify compares the four ids it has loaded with V
+// BEFORE it reads sdf through them, counts the offenders into a word of the tet workspace, and gof_mtets_classify returns
+// GOF_E_INVALID (count and emit refuse such a workspace), so no kernel dereferences sdf / vertices / scales through an unchecked id.
+// (torch wraps a negative id around and raises IndexError for id >= V; here both are refused.)
+// Scan and sort are the hand-written kernels of radix.hip -- no library primitives.
 #include "gof_common.h"
 #include "radix.h"
 #include <cstring>
@@ -38,10 +42,13 @@ constexpr int64_t MT_CHUNK = 32ll * 1024 * 1024;                             // 
 constexpr int MT_ITEMS = 16;                                                 // tets per thread in the counting passes
 constexpr int MT_BLOCK = 256 * MT_ITEMS;                                     // tets per workgroup there
 constexpr int MT_MAX_CHUNKS = 32;                                            // 6 * #tets < 2^32  ->  at most 23 chunks of 32 Mi tets
+constexpr int64_t MT_REFUSED = -2;                                           // counters[0] after a classification that found an id outside [0, V)
+static int64_t g_mt_chunk = MT_CHUNK;                                        // test support: gof_debug_mtets_chunk
 
 struct MtWs {
     uint8_t* tetcase;      // [Tt] 4-bit case index, 0xFF = not valid
     uint32_t* bsum;        // [3][nbp] per-block (4096 tets) counts of {valid, 1-triangle, 2-triangle} -> their exclusive scans
+                           // + [2] behind them: #tets with a vertex id outside [0, V), and 0xFFFFFFFF - (the first such tet)
                            // (nbp = #blocks + 1).  There are no per-tet scan arrays: the kernels that need a tet's rank rebuild the
                            // block-local scan from the case bytes (1 B per tet) on top of these block prefixes
     uint32_t* vt;          // [Tv] ids of the valid tets, ascending (compacted)
@@ -52,7 +59,7 @@ struct MtWs {
     uint32_t* uscan;       // [6*Tv+1] exclusive scan of "first occurrence"
     uint64_t* ukeys;       // [6*Tv] unique keys (min << 32 | max), ascending
     uint32_t* cscan;       // [6*Tv+1] exclusive scan of "crossing" over unique keys
-    int64_t* counters;     // [8] Tv, U, E, F1, F2
+    int64_t* counters;     // [8] Tv (or MT_REFUSED), U, E, F1, F2, V of the classification
     uint32_t* tmp;         // scan / sort scratch of the edge stage
     uint32_t* tmp_tet;     // scan scratch of the block counts
     size_t nbp;
@@ -77,7 +84,7 @@ static size_t mt_tet_layout(int64_t Tt, void* base, MtWs* w)
     const size_t n = (size_t)Tt;
     o.nbp = (n + 1 + MT_BLOCK - 1) / MT_BLOCK + 1;
     carve(p, o.tetcase, n);
-    carve(p, o.bsum, 3 * o.nbp);
+    carve(p, o.bsum, 3 * o.nbp + 2);
     carve(p, o.chunk_tab, 2 * (MT_MAX_CHUNKS + 1));
     carve(p, o.counters, 8);
     carve(p, o.tmp_tet, scan_tmp_words(o.nbp));
@@ -103,11 +110,19 @@ static size_t mt_edge_layout(int64_t Tv, void* base, MtWs* w)
 }
 
 __global__ void __launch_bounds__(256)
-mt_classify(int64_t Tt, const int64_t* __restrict__ tets, const float* __restrict__ sdf, uint8_t* __restrict__ tetcase)
+mt_classify(int64_t V, int64_t Tt, const int64_t* __restrict__ tets, const float* __restrict__ sdf, uint8_t* __restrict__ tetcase,
+            uint32_t* __restrict__ bad)
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= Tt) return;
     const longlong4 v = reinterpret_cast<const longlong4*>(tets)[t];
+    const uint64_t nv = (uint64_t)V;                                   // (a negative id is a huge unsigned one: one compare per id)
+    if ((uint64_t)v.x >= nv || (uint64_t)v.y >= nv || (uint64_t)v.z >= nv || (uint64_t)v.w >= nv) {
+        atomicAdd(&bad[0], 1u);
+        atomicMax(&bad[1], 0xFFFFFFFFu - (uint32_t)t);                 // -> the FIRST offending tet (t < 2^32 / 6)
+        tetcase[t] = (uint8_t)0xFF;                                    // no sdf read through such an id; the call is refused on the host
+        return;
+    }
     const int idx = (sdf[v.x] > 0 ? 1 : 0) | (sdf[v.y] > 0 ? 2 : 0) | (sdf[v.z] > 0 ? 4 : 0) | (sdf[v.w] > 0 ? 8 : 0);
     tetcase[t] = MT_NTRI[idx] ? (uint8_t)idx : (uint8_t)0xFF;          // 0 triangles for all-out / all-in (tetmesh.py:102)
 }
@@ -343,8 +358,8 @@ mt_write_faces(int64_t Tv, int64_t per_chunk, const int64_t* __restrict__ tets, 
 
 static inline int64_t per_chunk_of(int64_t Tt)
 {
-    if (Tt <= MT_CHUNK) return Tt > 0 ? Tt : 1;
-    const int64_t nchunks = Tt / MT_CHUNK + 1;          // torch.chunk(tets, Tt // chunk_size + 1), tetmesh.py:60
+    if (Tt <= g_mt_chunk) return Tt > 0 ? Tt : 1;
+    const int64_t nchunks = Tt / g_mt_chunk + 1;        // torch.chunk(tets, Tt // chunk_size + 1), tetmesh.py:60
     return (Tt + nchunks - 1) / nchunks;
 }
 
@@ -371,6 +386,24 @@ static int mt_check_sizes(int64_t V, int64_t Tt)
     return GOF_OK;
 }
 
+// count / emit: the counters gof_mtets_classify left in the tet workspace, refused unless they belong to an accepted classification of
+// tets over these V vertices (so that neither reads sdf / vertices / scales through an id that was not compared with this V)
+static int mt_accepted_counters(int64_t V, int64_t Tt, const void* tet_ws, size_t tet_ws_bytes, hipStream_t stream, int64_t cnt[6], MtWs* w)
+{
+    if (V == 0) { set_error("mtets: %lld tets but no vertices: every vertex id is outside [0, 0)", (long long)Tt); return GOF_E_INVALID; }
+    if (!tet_ws) { set_error("mtets: NULL input"); return GOF_E_INVALID; }
+    if (tet_ws_bytes < gof_mtets_tet_ws_bytes(Tt)) { set_error("mtets: tet workspace too small"); return GOF_E_WORKSPACE; }
+    mt_tet_layout(Tt, reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(const_cast<void*>(tet_ws)))), w);
+    GOF_HIP_CHECK(hipMemcpyAsync(cnt, w->counters, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    GOF_HIP_CHECK(hipStreamSynchronize(stream));
+    const int64_t Tv = cnt[0];
+    if (Tv == MT_REFUSED) { set_error("mtets: gof_mtets_classify refused these tets (a vertex id outside [0, V))"); return GOF_E_INVALID; }
+    if (Tv < 0 || Tv > Tt || cnt[3] < 0 || cnt[3] > Tv || cnt[4] < 0 || cnt[4] > Tv || cnt[3] + cnt[4] != Tv) {
+        set_error("mtets: the tet workspace holds no classification (run gof_mtets_classify first)"); return GOF_E_INVALID; }
+    if (cnt[5] != V) { set_error("mtets: the tet workspace was classified for %lld vertices, not %lld (run gof_mtets_classify again)", (long long)cnt[5], (long long)V); return GOF_E_INVALID; }
+    return GOF_OK;
+}
+
 int gof_mtets_classify(int64_t V, int64_t Tt, const int64_t* tets, const float* sdf, void* tet_ws, size_t tet_ws_bytes,
                        int64_t* num_valid_host, void* stream_)
 {
@@ -379,24 +412,50 @@ int gof_mtets_classify(int64_t V, int64_t Tt, const int64_t* tets, const float* 
     *num_valid_host = 0;
     if (int e = mt_check_sizes(V, Tt)) return e;
     if (Tt == 0) return GOF_OK;
-    if (!tets || !sdf || !tet_ws) { set_error("mtets: NULL input"); return GOF_E_INVALID; }
+    if (!tets || (!sdf && V > 0) || !tet_ws) { set_error("mtets: NULL input"); return GOF_E_INVALID; }
     if (tet_ws_bytes < gof_mtets_tet_ws_bytes(Tt)) { set_error("mtets: tet workspace too small"); return GOF_E_WORKSPACE; }
     MtWs w;
     mt_tet_layout(Tt, reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(tet_ws))), &w);
+    if (V == 0) {          // every id is outside [0, 0): refused without a launch; whatever classification the workspace held is void
+        const int64_t refused[6] = { MT_REFUSED, 0, 0, 0, 0, 0 };
+        GOF_HIP_CHECK(hipMemcpyAsync(w.counters, refused, sizeof(refused), hipMemcpyHostToDevice, stream));
+        GOF_HIP_CHECK(hipStreamSynchronize(stream));
+        set_error("mtets: %lld tets but no vertices: every vertex id is outside [0, 0)", (long long)Tt);
+        return GOF_E_INVALID;
+    }
     const dim3 blk(256);
     const uint32_t nbp = (uint32_t)w.nbp, nb = nbp - 1;
-    hipLaunchKernelGGL(mt_classify, dim3((unsigned)((Tt + 255) / 256)), blk, 0, stream, Tt, tets, sdf, w.tetcase);
+    uint32_t* const bad = w.bsum + 3 * (size_t)nbp;
+    GOF_HIP_CHECK(hipMemsetAsync(w.bsum, 0, (3 * (size_t)nbp + 2) * sizeof(uint32_t), stream));   // entry nb of each row stays 0 -> its scan = the total; the two words of `bad`
+    hipLaunchKernelGGL(mt_classify, dim3((unsigned)((Tt + 255) / 256)), blk, 0, stream, V, Tt, tets, sdf, w.tetcase, bad);
     GOF_LAUNCH_CHECK(stream, 0);
-    GOF_HIP_CHECK(hipMemsetAsync(w.bsum, 0, 3 * (size_t)nbp * sizeof(uint32_t), stream));   // entry nb of each row stays 0 -> its scan = the total
     hipLaunchKernelGGL(mt_count_blocks, dim3(nb), blk, 0, stream, Tt, w.tetcase, w.bsum, nbp);
     GOF_LAUNCH_CHECK(stream, 0);
     for (int k = 0; k < 3; k++)
         GOF_HIP_CHECK(device_scan_u32(w.bsum + (size_t)k * nbp, nullptr, w.bsum + (size_t)k * nbp, nbp, false, w.tmp_tet, nullptr, stream));
-    uint32_t host[3];
-    for (int k = 0; k < 3; k++)
+    uint32_t host[3], tail[3];
+    for (int k = 0; k < 2; k++)
         GOF_HIP_CHECK(hipMemcpyAsync(&host[k], w.bsum + (size_t)k * nbp + nb, 4, hipMemcpyDeviceToHost, stream));
+    // the total of row 2 is the last word of bsum's three rows and the two words of `bad` lie right behind it: they ride along in its copy
+    GOF_HIP_CHECK(hipMemcpyAsync(tail, w.bsum + 2 * (size_t)nbp + nb, sizeof(tail), hipMemcpyDeviceToHost, stream));
     GOF_HIP_CHECK(hipStreamSynchronize(stream));
-    const int64_t cnt[5] = { (int64_t)host[0], 0, 0, (int64_t)host[1], (int64_t)host[2] };
+    host[2] = tail[0];
+    const uint32_t hbad[2] = { tail[1], tail[2] };
+    if (hbad[0] != 0) {
+        // refused: mark the workspace (count / emit refuse it), then name the first offender (error path only: one 32-byte copy)
+        const int64_t refused[6] = { MT_REFUSED, 0, 0, 0, 0, V };
+        GOF_HIP_CHECK(hipMemcpyAsync(w.counters, refused, sizeof(refused), hipMemcpyHostToDevice, stream));
+        const int64_t t0 = (int64_t)(0xFFFFFFFFu - hbad[1]);
+        int64_t ids[4] = { 0, 0, 0, 0 };
+        GOF_HIP_CHECK(hipMemcpyAsync(ids, tets + 4 * t0, sizeof(ids), hipMemcpyDeviceToHost, stream));
+        GOF_HIP_CHECK(hipStreamSynchronize(stream));
+        int k = 0;
+        while (k < 3 && (uint64_t)ids[k] < (uint64_t)V) k++;
+        set_error("mtets: vertex id %lld (tet %lld, corner %d) is outside [0, %lld); %u of %lld tets have such an id",
+                  (long long)ids[k], (long long)t0, k, (long long)V, hbad[0], (long long)Tt);
+        return GOF_E_INVALID;
+    }
+    const int64_t cnt[6] = { (int64_t)host[0], 0, 0, (int64_t)host[1], (int64_t)host[2], V };
     GOF_HIP_CHECK(hipMemcpyAsync(w.counters, cnt, sizeof(cnt), hipMemcpyHostToDevice, stream));
     GOF_HIP_CHECK(hipStreamSynchronize(stream));
     *num_valid_host = host[0];
@@ -411,15 +470,12 @@ int gof_mtets_count(int64_t V, int64_t Tt, const int64_t* tets, const float* sdf
     *num_edges_host = 0; *num_faces_host = 0;
     if (int e = mt_check_sizes(V, Tt)) return e;
     if (Tt == 0) return GOF_OK;
-    if (!tets || !sdf || !tet_ws) { set_error("mtets: NULL input"); return GOF_E_INVALID; }
-    if (tet_ws_bytes < gof_mtets_tet_ws_bytes(Tt)) { set_error("mtets: tet workspace too small"); return GOF_E_WORKSPACE; }
     MtWs w;
-    mt_tet_layout(Tt, reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(tet_ws))), &w);
-    int64_t cnt[5];
-    GOF_HIP_CHECK(hipMemcpyAsync(cnt, w.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-    GOF_HIP_CHECK(hipStreamSynchronize(stream));
-    const int64_t Tv = cnt[0], F = cnt[3] + 2 * cnt[4];
-    if (Tv < 0 || Tv > Tt) { set_error("mtets: the tet workspace holds no classification (run gof_mtets_classify first)"); return GOF_E_INVALID; }
+    int64_t cnt[6];
+    if (int e = mt_accepted_counters(V, Tt, tet_ws, tet_ws_bytes, stream, cnt, &w)) return e;
+    if (!tets || !sdf) { set_error("mtets: NULL input"); return GOF_E_INVALID; }
+    const int64_t Tv = cnt[0];
+    const int64_t F = cnt[3] + 2 * cnt[4];               // (after the checks: a workspace that holds anything must not overflow here)
     const dim3 blk(256);
     const auto grid = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     const uint32_t nbp = (uint32_t)w.nbp, nb = nbp - 1;
@@ -456,7 +512,7 @@ int gof_mtets_count(int64_t V, int64_t Tt, const int64_t* tets, const float* sdf
         E = u32;
     }
     cnt[1] = U; cnt[2] = E;
-    GOF_HIP_CHECK(hipMemcpyAsync(w.counters, cnt, sizeof(cnt), hipMemcpyHostToDevice, stream));
+    GOF_HIP_CHECK(hipMemcpyAsync(w.counters, cnt, sizeof(cnt), hipMemcpyHostToDevice, stream));      // (all six: cnt[5] stays the V of the classification)
     GOF_HIP_CHECK(hipStreamSynchronize(stream));
     *num_edges_host = E;
     *num_faces_host = F;
@@ -468,29 +524,26 @@ int gof_mtets_emit(int64_t V, int64_t Tt, const int64_t* tets, const float* vert
                    int64_t* edge_ids, float* edge_pos, float* edge_sdf, float* edge_scales, int64_t* faces, void* stream_)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    (void)V;
-    if (Tt <= 0 || (num_edges == 0 && num_faces == 0)) return GOF_OK;
-    if (!tets || !vertices || !sdf || !scales || !tet_ws || !edge_ws || !edge_ids || !edge_pos || !edge_sdf || !edge_scales || !faces) {
-        set_error("mtets: NULL pointer"); return GOF_E_INVALID; }
-    if (tet_ws_bytes < gof_mtets_tet_ws_bytes(Tt)) { set_error("mtets: tet workspace too small"); return GOF_E_WORKSPACE; }
+    if (Tt <= 0) return GOF_OK;
     MtWs w;
-    mt_tet_layout(Tt, reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(tet_ws))), &w);
-    int64_t cnt[5];
-    GOF_HIP_CHECK(hipMemcpyAsync(cnt, w.counters, sizeof(cnt), hipMemcpyDeviceToHost, stream));
-    GOF_HIP_CHECK(hipStreamSynchronize(stream));
+    int64_t cnt[6];
+    if (int e = mt_accepted_counters(V, Tt, tet_ws, tet_ws_bytes, stream, cnt, &w)) return e;      // (also where there is nothing to write)
+    if (num_edges == 0 && num_faces == 0) return GOF_OK;
+    if (!tets || !vertices || !sdf || !scales || !edge_ws || !edge_ids || !edge_pos || !edge_sdf || !edge_scales || !faces) {
+        set_error("mtets: NULL pointer"); return GOF_E_INVALID; }
     const int64_t U = cnt[1];
-    if (cnt[2] != num_edges || cnt[3] + 2 * cnt[4] != num_faces) { set_error("mtets: counts do not match the workspace (run gof_mtets_count first)"); return GOF_E_INVALID; }
+    if (cnt[2] != num_edges || (int64_t)((uint64_t)cnt[3] + 2 * (uint64_t)cnt[4]) != num_faces) { set_error("mtets: counts do not match the workspace (run gof_mtets_count first)"); return GOF_E_INVALID; }
     if (cnt[0] > 0 && edge_ws_bytes < gof_mtets_edge_ws_bytes(cnt[0])) { set_error("mtets: edge workspace too small"); return GOF_E_WORKSPACE; }
     mt_edge_layout(cnt[0], reinterpret_cast<void*>(align_up(reinterpret_cast<size_t>(edge_ws))), &w);
     const dim3 blk(256);
     const auto grid = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    const int64_t per_chunk = per_chunk_of(Tt);
+    const int64_t nchunks = (Tt + per_chunk - 1) / per_chunk;
+    if (nchunks > MT_MAX_CHUNKS) { set_error("mtets: too many chunks of tets (%lld, at most %d)", (long long)nchunks, MT_MAX_CHUNKS); return GOF_E_INVALID; }
     if (U > 0) {
         hipLaunchKernelGGL(mt_write_edges, grid(U), blk, 0, stream, U, w.ukeys, w.cscan, vertices, sdf, scales, edge_ids, edge_pos, edge_sdf, edge_scales);
         GOF_LAUNCH_CHECK(stream, 0);
     }
-    const int64_t per_chunk = per_chunk_of(Tt);
-    const int64_t nchunks = (Tt + per_chunk - 1) / per_chunk;
-    if (nchunks > MT_MAX_CHUNKS) { set_error("mtets: too many 32 Mi-tet chunks (%lld)", (long long)nchunks); return GOF_E_INVALID; }
     const uint32_t nbp = (uint32_t)w.nbp;
     hipLaunchKernelGGL(mt_chunk_table, dim3((unsigned)nchunks + 1), blk, 0, stream, Tt, per_chunk, w.tetcase, w.bsum, nbp, w.chunk_tab);
     GOF_LAUNCH_CHECK(stream, 0);
@@ -498,6 +551,15 @@ int gof_mtets_emit(int64_t V, int64_t Tt, const int64_t* tets, const float* vert
         hipLaunchKernelGGL(mt_write_faces, grid(cnt[0]), blk, 0, stream, cnt[0], per_chunk, tets, w.tetcase, w.vt, w.frank, w.chunk_tab, U, w.ukeys, w.cscan, faces);
     GOF_LAUNCH_CHECK(stream, 0);
     return GOF_OK;
+}
+
+// test support (the debug family): the tets-per-chunk threshold of per_chunk_of() for the calls that follow, so that the chunk
+// arithmetic (mt_chunk_table, fidx in mt_write_faces) can be walked at small sizes.  Returns the previous value; <= 0 restores 32 Mi.
+int64_t gof_debug_mtets_chunk(int64_t chunk_size)
+{
+    const int64_t prev = g_mt_chunk;
+    g_mt_chunk = chunk_size > 0 ? chunk_size : MT_CHUNK;
+    return prev;
 }
 
 } // extern "C"

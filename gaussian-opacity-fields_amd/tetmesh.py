@@ -10,6 +10,10 @@ Same signature and return structure::
 The work is done by ``gof_mtets_classify`` / ``gof_mtets_count`` / ``gof_mtets_emit`` of libgof_hip.so (csrc/mtets.hip): crossing
 edges unique and sorted by (min id, max id) exactly as ``torch.unique(dim=0)`` orders them, faces in
 the reference's order (per 32 Mi-tet chunk: 1-triangle tets first, then 2-triangle tets).
+
+Every vertex id in ``tets`` must lie in ``[0, num_vertices)``: the library checks all of them on the device before it reads anything
+through one and raises (``GofError``, naming the first offending tet) otherwise.  This departs from torch, where the reference raises
+IndexError for an id >= num_vertices but lets a negative id wrap around to the end of the vertex array.
 """
 import ctypes as C
 

@@ -378,7 +378,17 @@ int gof_sh_grad_expand(int32_t P, int32_t D, int32_t M, int32_t n_views, const f
  * Phase 2, gof_mtets_emit: edge end-point ids [E,2] (int64), end-point positions [E,2,3], end-point sdf [E,2], end-point scales
  *   [E,2] and faces [F,3] (int64) in the reference's order (per 32 Mi-tet chunk all 1-triangle tets first, then the 2-triangle
  *   tets; tetmesh.py:55-95, 126-136).
- * Vertex ids must be < 2^32 and 6 * num_tets < 2^32. */
+ * num_verts must be < 2^32 and 6 * num_tets < 2^32.
+ * Every vertex id of `tets` must lie in [0, num_verts).  gof_mtets_classify checks all of them on the device before anything is read
+ *   through one: an id < 0 or >= num_verts (num_verts == 0 with num_tets > 0 included) makes it return GOF_E_INVALID, gof_last_error()
+ *   naming the first offending tet, its id and the number of offending tets; *num_valid_tets_host is 0 and the tet workspace is
+ *   marked refused (whatever classification it held before is void).  gof_mtets_count and gof_mtets_emit read that mark before they
+ *   launch anything and return GOF_E_INVALID without writing an output -- gof_mtets_emit also where num_edges == num_faces == 0 --
+ *   for a refused tet workspace, for num_verts == 0 with num_tets > 0, for a tet workspace that holds no classification, and for one
+ *   that was classified with another num_verts (the ids were compared with that number, not this one).  Both need the tet workspace
+ *   (non-NULL, at least gof_mtets_tet_ws_bytes(num_tets): GOF_E_INVALID / GOF_E_WORKSPACE otherwise) whenever num_tets > 0.
+ *   This departs from torch, where the reference raises IndexError for id >= num_verts but wraps a negative id around (tets[-1] is
+ *   the last vertex). */
 size_t gof_mtets_tet_ws_bytes(int64_t num_tets);
 size_t gof_mtets_edge_ws_bytes(int64_t num_valid_tets);
 int gof_mtets_classify(int64_t num_verts, int64_t num_tets, const int64_t* tets /* [Tt,4] */, const float* sdf /* [V] */,
@@ -410,6 +420,10 @@ int gof_profile_report(char* buf, size_t cap);
 int64_t gof_debug_fetch(const char* name, const GofRasterArgs* args, uint32_t num_rendered,
                         const void* geom_ws, const void* binning_ws, const void* image_ws,
                         void* dst, size_t dst_bytes, void* stream);
+/* Test support, NOT part of the product's contract (may change with the tests): the number of tets above which gof_mtets_emit orders
+ * the faces chunk by chunk (32 Mi, tetmesh.py:55) is replaced by `chunk_size` for the calls that follow, so that the chunk arithmetic
+ * can be tested at small sizes.  Returns the previous value; chunk_size <= 0 restores 32 Mi.  Process-wide, not thread-safe. */
+int64_t gof_debug_mtets_chunk(int64_t chunk_size);
 
 #ifdef __cplusplus
 }

@@ -43,7 +43,8 @@ int64_t gofref_fetch(const GofRefState* s, const char* name, void* dst, size_t d
 /* marching tetrahedra restatement (utils/tetmesh.py:47-138), see gof_oracle_mtets.inc */
 int gofref_mtets(int64_t V, int64_t Tt, const int64_t* tets, const float* vertices, const float* sdf, const float* scales,
                  int64_t* num_edges, int64_t* num_faces,
-                 int64_t* edge_ids /*cap*/, float* edge_pos, float* edge_sdf, float* edge_scales, int64_t* faces, int64_t cap_edges, int64_t cap_faces);
+                 int64_t* edge_ids /*cap*/, float* edge_pos, float* edge_sdf, float* edge_scales, int64_t* faces, int64_t cap_edges, int64_t cap_faces,
+                 int64_t chunk_size /* tets per chunk of tetmesh.py:55; <= 0: the reference's 32 Mi */);
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ const int mt_base_tet_edges[12] = { 0,1, 0,2, 0,3, 1,2, 1,3, 2,3 };    // :43
 extern "C" int gofref_mtets(int64_t V, int64_t Tt, const int64_t* tets, const float* vertices, const float* sdf, const float* scales,
                             int64_t* num_edges, int64_t* num_faces,
                             int64_t* edge_ids, float* edge_pos, float* edge_sdf, float* edge_scales, int64_t* faces,
-                            int64_t cap_edges, int64_t cap_faces)
+                            int64_t cap_edges, int64_t cap_faces, int64_t chunk_size_arg)
 {
     (void)V;
     struct E { int64_t a, b; };
@@ -65,7 +65,7 @@ extern "C" int gofref_mtets(int64_t V, int64_t Tt, const int64_t* tets, const fl
         }
     }
     // faces: chunk by chunk (:55-57: torch.chunk(tets, Tt // chunk + 1) when Tt > chunk)
-    const int64_t chunk_size = 32ll * 1024 * 1024;
+    const int64_t chunk_size = chunk_size_arg > 0 ? chunk_size_arg : 32ll * 1024 * 1024;      // (:55; smaller only for the chunk tests)
     int64_t nchunks = 1, per = Tt;
     if (Tt > chunk_size) { nchunks = Tt / chunk_size + 1; per = (Tt + nchunks - 1) / nchunks; }
     int64_t fo = 0;

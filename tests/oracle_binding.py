@@ -60,7 +60,7 @@ def lib():
         L.gofref_num_integrated.argtypes = [C.c_void_p]
         L.gofref_fetch.restype = C.c_int64
         L.gofref_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]
-        L.gofref_mtets.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.POINTER(C.c_int64)] * 2 + [C.c_void_p] * 5 + [C.c_int64] * 2
+        L.gofref_mtets.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.POINTER(C.c_int64)] * 2 + [C.c_void_p] * 5 + [C.c_int64] * 3
         _lib = L
     return _lib
 
@@ -200,16 +200,17 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     return out.astype(bool)
 
 
-def marching_tets(vertices, tets, sdf, scales):
+def marching_tets(vertices, tets, sdf, scales, chunk_size=0):
+    """chunk_size: tets per chunk of the reference's chunk loop (utils/tetmesh.py:55); 0 = its own 32 Mi"""
     v = _f32(vertices); t = np.ascontiguousarray(tets, dtype=np.int64); s = _f32(sdf).reshape(-1); sc = _f32(scales).reshape(-1)
     ne, nf = C.c_int64(), C.c_int64()
     L = lib()
-    rc = L.gofref_mtets(v.shape[0], t.shape[0], _p(t), _p(v), _p(s), _p(sc), C.byref(ne), C.byref(nf), None, None, None, None, None, 0, 0)
+    rc = L.gofref_mtets(v.shape[0], t.shape[0], _p(t), _p(v), _p(s), _p(sc), C.byref(ne), C.byref(nf), None, None, None, None, None, 0, 0, int(chunk_size))
     assert rc == 0
     E, F = ne.value, nf.value
     ids = np.zeros((E, 2), np.int64); pos = np.zeros((E, 2, 3), np.float32); esdf = np.zeros((E, 2), np.float32)
     esc = np.zeros((E, 2), np.float32); faces = np.zeros((F, 3), np.int64)
-    rc = L.gofref_mtets(v.shape[0], t.shape[0], _p(t), _p(v), _p(s), _p(sc), C.byref(ne), C.byref(nf), _p(ids), _p(pos), _p(esdf), _p(esc), _p(faces), E, F)
+    rc = L.gofref_mtets(v.shape[0], t.shape[0], _p(t), _p(v), _p(s), _p(sc), C.byref(ne), C.byref(nf), _p(ids), _p(pos), _p(esdf), _p(esc), _p(faces), E, F, int(chunk_size))
     assert rc == 0
     return ids, pos, esdf, esc, faces
 
