@@ -15,18 +15,18 @@
 //     ranges of 3 cells, one binary search each): a kept one removes it, none undecided keeps it.  States move undecided -> decided
 //     only, so a stale read is conservative and the result does not depend on the schedule.
 // (c) knn.hip's structure in fp64 with two clouds: the reference cloud in Morton order, boxes of 256 / groups of 32 boxes with fp64
-//     bounds; the queries are sorted by Morton code of the SAME bounding box (clamped), so a workgroup's 256 queries are neighbours;
-//     a first bound from the query's Morton neighbours in the sorted reference; then groups / boxes whose conservative distance does
-//     not exceed the bound are staged in LDS (256 x (24 + 4) B = 7 KB) and scanned.  Pruning is exact: every operation of the box
-//     distance is monotone in |difference| (knn.hip's argument, any IEEE format), so fl(box distance) <= fl(distance to any point of
-//     the box); a box is skipped only if that exceeds the best so far, ties are visited and resolved to the smallest index.
+//     bounds (box_index.h, the one definition both units use); the queries are sorted by Morton code of the SAME bounding box
+//     (clamped), so a workgroup's 256 queries are neighbours; a first bound from the query's Morton neighbours in the sorted
+//     reference; then groups / boxes whose conservative distance does not exceed the bound are staged in LDS (256 x (24 + 4) B =
+//     7 KB) and scanned.  Pruning is exact (box_dist, box_index.h): a box is skipped only if its distance exceeds the best so far,
+//     ties are visited and resolved to the smallest index.
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cmath>
 #include "../../include/gof_hip.h"
 #include "../../include/gof_cloud_hip.h"
 #include "radix.h"
-#include "gof_geom.h"
+#include "box_index.h"
 
 namespace gof {
 
@@ -340,18 +340,8 @@ static size_t thin_layout(int64_t N, void* base, ThinWs* out)
 // =====================================================================================================================================
 // (c) nearest neighbour between two clouds
 // =====================================================================================================================================
-constexpr int NN_BOX = 256;
-constexpr int NN_GROUP = 32;
-struct NnBox { double lo[3]; double hi[3]; };
+typedef Box3<double> NnBox;
 
-__device__ __forceinline__ uint32_t nn_spread(uint32_t x)
-{
-    x = (x | (x << 16)) & 0x030000FF;
-    x = (x | (x << 8)) & 0x0300F00F;
-    x = (x | (x << 4)) & 0x030C30C3;
-    x = (x | (x << 2)) & 0x09249249;
-    return x;
-}
 // 30-bit Morton code in the bounding box hdr[0..5] (points outside it -- queries -- are clamped: the order only affects the speed)
 __global__ void __launch_bounds__(256)
 nn_morton(int64_t N, const double* __restrict__ pts, const u64* __restrict__ box_hdr, uint32_t* __restrict__ codes, uint32_t* __restrict__ idx,
@@ -368,73 +358,37 @@ nn_morton(int64_t N, const double* __restrict__ pts, const u64* __restrict__ box
         const double lo = unordered64(box_hdr[c]), hi = unordered64(box_hdr[3 + c]);
         const double ext = hi - lo;
         const double cell = ext > 0.0 ? ((p[c] - lo) / ext) * 1023.0 : 0.0;
-        code |= nn_spread((uint32_t)fmin(fmax(cell, 0.0), 1023.0)) << c;
+        code |= morton_spread10((uint32_t)fmin(fmax(cell, 0.0), 1023.0)) << c;
     }
     codes[i] = code;
     idx[i] = (uint32_t)i;
 }
 
-__global__ void __launch_bounds__(NN_BOX)
+__global__ void __launch_bounds__(BOX_POINTS)
 nn_gather_boxes(int64_t N, const double* __restrict__ pts, const uint32_t* __restrict__ order, const uint32_t* __restrict__ codes,
                 double* __restrict__ sorted, uint32_t* __restrict__ sidx, uint32_t* __restrict__ scodes, NnBox* __restrict__ boxes)
 {
-    const int64_t i = (int64_t)blockIdx.x * NN_BOX + threadIdx.x;
-    double lo[3] = { DBL_MAX, DBL_MAX, DBL_MAX }, hi[3] = { -DBL_MAX, -DBL_MAX, -DBL_MAX };
+    const int64_t i = (int64_t)blockIdx.x * BOX_POINTS + threadIdx.x;
+    NnBox b = box_empty<double>();
     if (i < N) {
         const int64_t s = order[i];
 #pragma unroll
-        for (int c = 0; c < 3; c++) { const double v = pts[3 * s + c]; sorted[3 * i + c] = v; lo[c] = hi[c] = v; }
+        for (int c = 0; c < 3; c++) { const double v = pts[3 * s + c]; sorted[3 * i + c] = v; b.lo[c] = b.hi[c] = v; }
         sidx[i] = (uint32_t)s;
         scodes[i] = codes[i];
     }
-    __shared__ double s_lo[3][NN_BOX / 64], s_hi[3][NN_BOX / 64];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        for (int o = 32; o > 0; o >>= 1) { lo[c] = fmin(lo[c], __shfl_xor(lo[c], o)); hi[c] = fmax(hi[c], __shfl_xor(hi[c], o)); }
-        if ((threadIdx.x & 63) == 0) { s_lo[c][threadIdx.x >> 6] = lo[c]; s_hi[c][threadIdx.x >> 6] = hi[c]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        NnBox b;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            b.lo[c] = fmin(fmin(s_lo[c][0], s_lo[c][1]), fmin(s_lo[c][2], s_lo[c][3]));
-            b.hi[c] = fmax(fmax(s_hi[c][0], s_hi[c][1]), fmax(s_hi[c][2], s_hi[c][3]));
-        }
-        boxes[blockIdx.x] = b;
-    }
+    __shared__ double s_lo[3][BOX_POINTS / 64], s_hi[3][BOX_POINTS / 64];
+    b = block_box(b.lo, b.hi, s_lo, s_hi);
+    if (threadIdx.x == 0) boxes[blockIdx.x] = b;
 }
 
 __global__ void __launch_bounds__(64)
 nn_group_boxes(int64_t num_boxes, const NnBox* __restrict__ boxes, NnBox* __restrict__ groups)
 {
-    const int64_t g = blockIdx.x;
-    const int64_t b = g * NN_GROUP + (threadIdx.x & (NN_GROUP - 1));
-    double lo[3] = { DBL_MAX, DBL_MAX, DBL_MAX }, hi[3] = { -DBL_MAX, -DBL_MAX, -DBL_MAX };
-    if (b < num_boxes && threadIdx.x < NN_GROUP) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) { lo[c] = boxes[b].lo[c]; hi[c] = boxes[b].hi[c]; }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        for (int o = 32; o > 0; o >>= 1) { lo[c] = fmin(lo[c], __shfl_xor(lo[c], o)); hi[c] = fmax(hi[c], __shfl_xor(hi[c], o)); }
-    if (threadIdx.x == 0) {
-        NnBox r;
-#pragma unroll
-        for (int c = 0; c < 3; c++) { r.lo[c] = lo[c]; r.hi[c] = hi[c]; }
-        groups[g] = r;
-    }
+    const NnBox r = group_box(num_boxes, boxes, (int64_t)blockIdx.x);
+    if (threadIdx.x == 0) groups[blockIdx.x] = r;
 }
 
-// conservative: each operation is monotone in |difference|, so fl(this) <= fl(distance to any point inside the box)
-__device__ __forceinline__ double nn_box_dist(const NnBox& box, double px, double py, double pz)
-{
-    double dx = 0.0, dy = 0.0, dz = 0.0;
-    if (px < box.lo[0] || px > box.hi[0]) dx = fmin(fabs(px - box.lo[0]), fabs(px - box.hi[0]));
-    if (py < box.lo[1] || py > box.hi[1]) dy = fmin(fabs(py - box.lo[1]), fabs(py - box.hi[1]));
-    if (pz < box.lo[2] || pz > box.hi[2]) dz = fmin(fabs(pz - box.lo[2]), fabs(pz - box.hi[2]));
-    return (dx * dx + dy * dy) + dz * dz;
-}
 __device__ __forceinline__ void nn_update(double px, double py, double pz, double cx, double cy, double cz, uint32_t ci, double& best, uint32_t& besti)
 {
     const double dx = cx - px, dy = cy - py, dz = cz - pz;
@@ -442,15 +396,15 @@ __device__ __forceinline__ void nn_update(double px, double py, double pz, doubl
     if (d < best || (d == best && ci < besti)) { best = d; besti = ci; }
 }
 
-__global__ void __launch_bounds__(NN_BOX)
+__global__ void __launch_bounds__(BOX_POINTS)
 nn_search(int64_t NQ, const double* __restrict__ query, const uint32_t* __restrict__ qorder, const uint32_t* __restrict__ qcodes,
           int64_t NS, const double* __restrict__ sorted, const uint32_t* __restrict__ sidx, const uint32_t* __restrict__ scodes,
           const NnBox* __restrict__ boxes, const NnBox* __restrict__ groups, int64_t num_boxes, int64_t num_groups,
           double* __restrict__ dist, int32_t* __restrict__ nearest, u64* __restrict__ hdr)
 {
-    __shared__ double s_pts[NN_BOX * 3];
-    __shared__ uint32_t s_idx[NN_BOX];
-    const int64_t i = (int64_t)blockIdx.x * NN_BOX + threadIdx.x;
+    __shared__ double s_pts[BOX_POINTS * 3];
+    __shared__ uint32_t s_idx[BOX_POINTS];
+    const int64_t i = (int64_t)blockIdx.x * BOX_POINTS + threadIdx.x;
     const bool valid = i < NQ;
     int64_t qi = 0;
     double qx = 0.0, qy = 0.0, qz = 0.0;
@@ -470,14 +424,14 @@ nn_search(int64_t NQ, const double* __restrict__ query, const uint32_t* __restri
         }
     }
     for (int64_t g = 0; g < num_groups; g++) {
-        const bool need_g = valid && !(nn_box_dist(groups[g], qx, qy, qz) > best);
+        const bool need_g = valid && !(box_dist(groups[g], qx, qy, qz) > best);
         if (!__syncthreads_or(need_g)) continue;
-        const int64_t b1 = min(num_boxes, (g + 1) * NN_GROUP);
-        for (int64_t b = g * NN_GROUP; b < b1; b++) {
-            const bool need = valid && !(nn_box_dist(boxes[b], qx, qy, qz) > best);
+        const int64_t b1 = min(num_boxes, (g + 1) * BOX_GROUP);
+        for (int64_t b = g * BOX_GROUP; b < b1; b++) {
+            const bool need = valid && !(box_dist(boxes[b], qx, qy, qz) > best);
             if (!__syncthreads_or(need)) continue;                     // (also the barrier before restaging)
-            const int64_t j0 = b * NN_BOX;
-            const int cnt = (int)min((int64_t)NN_BOX, NS - j0);
+            const int64_t j0 = b * BOX_POINTS;
+            const int cnt = (int)min((int64_t)BOX_POINTS, NS - j0);
             if ((int)threadIdx.x < cnt) {
                 const int64_t j = j0 + threadIdx.x;
                 s_pts[3 * threadIdx.x] = sorted[3 * j]; s_pts[3 * threadIdx.x + 1] = sorted[3 * j + 1]; s_pts[3 * threadIdx.x + 2] = sorted[3 * j + 2];
@@ -511,7 +465,7 @@ struct NnIndex { u64* hdr; double* sorted; uint32_t* sidx; uint32_t* scodes; NnB
 static size_t nn_index_layout(int64_t NS, void* base, NnIndex* out)
 {
     const size_t n = (size_t)(NS < 1 ? 1 : NS);
-    const size_t nb = (n + NN_BOX - 1) / NN_BOX, ng = (nb + NN_GROUP - 1) / NN_GROUP;
+    const int64_t nb = box_count((int64_t)n), ng = group_count(nb);
     Carver c{ static_cast<char*>(base), 0 };
     NnIndex w;
     w.hdr = c.take<u64>(HDR_WORDS);
@@ -684,13 +638,13 @@ int gof_cloud_nn_build(int64_t NS, const double* ref, void* index, size_t index_
     GOF_LAUNCH_CHECK(stream, 0);
     if (NS == 0) return GOF_OK;
     GOF_PROFILE("cloud_nn_build", stream);
-    const int64_t nb = (NS + NN_BOX - 1) / NN_BOX, ng = (nb + NN_GROUP - 1) / NN_GROUP;
+    const int64_t nb = box_count(NS), ng = group_count(nb);
     hipLaunchKernelGGL(cloud_bbox, dim3((unsigned)min((int64_t)2048, (NS + 255) / 256)), dim3(256), 0, stream, NS, ref, w.hdr);
     hipLaunchKernelGGL(nn_morton, grid_of(NS), dim3(256), 0, stream, NS, ref, w.hdr, w.ka, w.va, w.hdr);
     GOF_LAUNCH_CHECK(stream, 0);
     uint32_t *kr = nullptr, *vr = nullptr;
     GOF_HIP_CHECK(radix_sort_pairs_u32(w.ka, w.va, w.kb, w.vb, (size_t)NS, 30, w.tmp, &kr, &vr, stream));
-    hipLaunchKernelGGL(nn_gather_boxes, dim3((unsigned)nb), dim3(NN_BOX), 0, stream, NS, ref, vr, kr, w.sorted, w.sidx, w.scodes, w.boxes);
+    hipLaunchKernelGGL(nn_gather_boxes, dim3((unsigned)nb), dim3(BOX_POINTS), 0, stream, NS, ref, vr, kr, w.sorted, w.sidx, w.scodes, w.boxes);
     hipLaunchKernelGGL(nn_group_boxes, dim3((unsigned)ng), dim3(64), 0, stream, nb, w.boxes, w.groups);
     GOF_LAUNCH_CHECK(stream, 0);
     u64 flags = 0;
@@ -721,12 +675,12 @@ int gof_cloud_nn_query(int64_t NS, const void* index, size_t index_bytes, int64_
         GOF_LAUNCH_CHECK(stream, 0);
         return GOF_OK;
     }
-    const int64_t nb = (NS + NN_BOX - 1) / NN_BOX, ng = (nb + NN_GROUP - 1) / NN_GROUP;
+    const int64_t nb = box_count(NS), ng = group_count(nb);
     hipLaunchKernelGGL(nn_morton, grid_of(NQ), dim3(256), 0, stream, NQ, query, x.hdr, w.ka, w.va, w.hdr);
     GOF_LAUNCH_CHECK(stream, 0);
     uint32_t *kr = nullptr, *vr = nullptr;
     GOF_HIP_CHECK(radix_sort_pairs_u32(w.ka, w.va, w.kb, w.vb, (size_t)NQ, 30, w.tmp, &kr, &vr, stream));
-    hipLaunchKernelGGL(nn_search, dim3((unsigned)((NQ + NN_BOX - 1) / NN_BOX)), dim3(NN_BOX), 0, stream, NQ, query, vr, kr, NS, x.sorted, x.sidx,
+    hipLaunchKernelGGL(nn_search, dim3((unsigned)box_count(NQ)), dim3(BOX_POINTS), 0, stream, NQ, query, vr, kr, NS, x.sorted, x.sidx,
                        x.scodes, x.boxes, x.groups, nb, ng, dist, nearest, w.hdr);
     GOF_LAUNCH_CHECK(stream, 0);
     u64 flags = 0;

@@ -18,6 +18,7 @@
 #include <cstring>
 #include "gof_common.h"
 #include "radix.h"
+#include "gof_geom.h"
 #include "delaunay_predicates.h"
 #include "../../include/gof_delaunay_hip.h"
 
@@ -259,24 +260,7 @@ __device__ __forceinline__ unsigned long long nominee_key(uint32_t q)
     return ((unsigned long long)hi << 32) | q;
 }
 
-__device__ __forceinline__ uint32_t float_key(float f)
-{
-    uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);     // -0 and +0 are one coordinate
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_float(uint32_t k)
-{
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-__device__ __forceinline__ uint32_t spread3(uint32_t x)
-{
-    x &= 0x3FF;
-    x = (x | (x << 16)) & 0x030000FF;
-    x = (x | (x << 8)) & 0x0300F00F;
-    x = (x | (x << 4)) & 0x030C30C3;
-    x = (x | (x << 2)) & 0x09249249;
-    return x;
-}
+__device__ __forceinline__ uint32_t float_key(float f) { return ordered32(f == 0.0f ? 0.0f : f); }     // -0 and +0 are one coordinate
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // dedup and Morton order
@@ -352,7 +336,7 @@ __global__ void __launch_bounds__(DT_THREADS) dt_extremes(const float* __restric
         const float* q = pts + 3 * (size_t)ids[i];
         double t[3];
         for (int k = 0; k < 3; k++) {
-            const double lo = key_float(hdr->bbox[k]), hi = key_float(hdr->bbox[3 + k]);
+            const double lo = unordered32(hdr->bbox[k]), hi = unordered32(hdr->bbox[3 + k]);
             t[k] = hi > lo ? ((double)q[k] - lo) / (hi - lo) : 0.0;
         }
         for (int d = 0; d < DT_DIRS; d++) {
@@ -383,11 +367,11 @@ __global__ void __launch_bounds__(DT_THREADS) dt_morton(const float* __restrict_
     const float* q = pts + 3 * (size_t)ids[i];
     uint32_t code = 0;
     for (int k = 0; k < 3; k++) {
-        const double lo = key_float(hdr->bbox[k]), hi = key_float(hdr->bbox[3 + k]);
+        const double lo = unordered32(hdr->bbox[k]), hi = unordered32(hdr->bbox[3 + k]);
         const double ext = hi - lo;
         double t = ext > 0 ? ((double)q[k] - lo) / ext * 1023.0 : 0.0;
         const uint32_t c = t <= 0 ? 0u : t >= 1023.0 ? 1023u : (uint32_t)t;
-        code |= spread3(c) << k;
+        code |= morton_spread10(c & 0x3FF) << k;
     }
     key[i] = extreme[i] ? 0u : code + 1;
     val[i] = ids[i];

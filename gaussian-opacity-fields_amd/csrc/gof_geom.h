@@ -1,8 +1,9 @@
-// gof_geom.h -- what the stand-alone geometry units (knn, tsdf, cloud, cloud_reg, mesh_cull) share besides radix.h: the ordered
-// encoding of fp64 for integer atomics, the 64-bit wave sum, and the host-side plumbing of a C-ABI entry point (count check,
-// workspace alignment and carving, the launch grid of one thread per item, the buffers of radix.h's 63-bit key sort).  Included by
-// those five units and radix.hip only -- neither gof_common.h nor radix.h includes it -- so an edit here cannot reach the units of
-// the training step (tests/devtools/dev_same_isa.py watches the two headers they do include).
+// gof_geom.h -- what the stand-alone geometry units (knn, tsdf, cloud, cloud_reg, mesh_cull, delaunay) share besides radix.h: the
+// ordered encodings of fp32 / fp64 for integer atomics and sort keys, the 10-bit Morton spread, the 64-bit wave sum, and the host-side
+// plumbing of a C-ABI entry point (count check, workspace alignment and carving, the launch grid of one thread per item, the buffers
+// of radix.h's 63-bit key sort).  Included by those six units, box_index.h (knn and cloud) and radix.hip only -- neither gof_common.h
+// nor radix.h includes it -- so an edit here cannot reach the units of the training step (tests/devtools/dev_same_isa.py watches the
+// two headers they do include).
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -13,10 +14,21 @@ namespace gof {
 typedef unsigned long long u64;
 
 // ---- device ------------------------------------------------------------------------------------------------------------------------
-// fp64 <-> u64 whose unsigned order is the order of the doubles (atomicMin / atomicMax on coordinates)
+// fp32 <-> u32 and fp64 <-> u64 whose unsigned order is the order of the floats (atomicMin / atomicMax on coordinates, sort keys)
+__device__ __forceinline__ uint32_t ordered32(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+__device__ __forceinline__ float unordered32(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
 __device__ __forceinline__ u64 ordered64(double d) { const u64 b = (u64)__double_as_longlong(d); return (b >> 63) ? ~b : (b | 0x8000000000000000ull); }
 __device__ __forceinline__ double unordered64(u64 u) { return __longlong_as_double((long long)((u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u)); }
 __device__ __forceinline__ bool finite3(double x, double y, double z) { return fabs(x) <= DBL_MAX && fabs(y) <= DBL_MAX && fabs(z) <= DBL_MAX; }
+// bits 0..9 of x to bits 0, 3, .., 27: one axis of a 30-bit Morton code (simple_knn.cu:39-46).  x < 1024: the caller masks or clamps
+__device__ __forceinline__ uint32_t morton_spread10(uint32_t x)
+{
+    x = (x | (x << 16)) & 0x030000FF;
+    x = (x | (x << 8)) & 0x0300F00F;
+    x = (x | (x << 4)) & 0x030C30C3;
+    x = (x | (x << 2)) & 0x09249249;
+    return x;
+}
 // the wave's sum in every lane (all 64 lanes must call)
 __device__ __forceinline__ u64 wave_sum(u64 v)
 {

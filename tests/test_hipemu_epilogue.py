@@ -256,8 +256,8 @@ def _cloud(n, seed, kind="uniform"):
     return test_knn._cloud(n, seed, kind)
 
 
-KNN_CASES = [(1, "uniform"), (2, "uniform"), (3, "uniform"), (4, "uniform"), (255, "uniform"), (257, "uniform"),
-             (5000, "uniform"), (6000, "clustered"), (3000, "line"), (4000, "duplicates")]
+KNN_CASES = [(1, "uniform"), (2, "uniform"), (3, "uniform"), (4, "uniform"), (255, "uniform"), (256, "uniform"), (257, "uniform"),
+             (5000, "uniform"), (8192, "uniform"), (8193, "uniform"), (6000, "clustered"), (3000, "line"), (4000, "duplicates")]
 
 
 @pytest.mark.parametrize("n,kind", KNN_CASES)

@@ -71,8 +71,9 @@ def _product(pts):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,kind", [(1, "uniform"), (2, "uniform"), (3, "uniform"), (4, "uniform"), (255, "uniform"), (257, "uniform"),
-                                    (5000, "uniform"), (100_000, "uniform"), (60_000, "clustered"), (30_000, "line"), (20_000, "duplicates")])
+@pytest.mark.parametrize("n,kind", [(1, "uniform"), (2, "uniform"), (3, "uniform"), (4, "uniform"), (255, "uniform"), (256, "uniform"),
+                                    (257, "uniform"), (5000, "uniform"), (8192, "uniform"), (8193, "uniform"), (100_000, "uniform"),
+                                    (60_000, "clustered"), (30_000, "line"), (20_000, "duplicates")])
 def test_matches_oracle(n, kind):
     pts = _cloud(n, n + len(kind), kind)
     got, ref = _product(pts), KO.mean_dist3(pts)

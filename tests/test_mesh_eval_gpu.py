@@ -81,7 +81,7 @@ def test_thinning_equals_the_sequential_loop(name):
     assert M.last_stats()["thin"]["kept"] == want.sum()
 
 
-@pytest.mark.parametrize("name", ["clouds", "ties", "far", "one", "empty", "scales"])
+@pytest.mark.parametrize("name", ["clouds", "ties", "far", "one", "empty", "scales", "groups"])
 def test_nearest_is_exact(name):
     import mesh_eval as M
     Q, S = H.nn_case(name)
@@ -95,7 +95,7 @@ def test_nearest_is_exact(name):
     pick = np.random.default_rng(0).permutation(len(Q))[:400]
     db, ib = R.nearest_brute(Q[pick], S)
     assert np.array_equal(bits(d[pick]), bits(db)) and np.array_equal(i[pick], ib)
-    if name in ("clouds", "far", "scales"):
+    if name in ("clouds", "far", "scales", "groups"):
         assert np.array_equal(i, ir)
 
 

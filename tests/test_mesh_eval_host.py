@@ -113,6 +113,8 @@ def nn_case(name):
         S = np.vstack([rng.random((3000, 3)) * 1e-3, rng.random((3000, 3)) * 1e3])
         Q = np.vstack([rng.random((1000, 3)) * 1e-3, rng.random((1000, 3)) * 1e3, rng.random((500, 3))])
         return Q, S
+    if name == "groups":                                  # 32 full boxes = one full group, then a 33rd box of one point in a second group
+        return rng.random((257, 3)), rng.random((8193, 3))
     raise KeyError(name)
 
 
@@ -281,7 +283,7 @@ def test_thinning_does_not_depend_on_the_schedule(name, order, tmp_path):
     assert np.array_equal(_emulate("thin:" + name, tmp_path, order=order)["keep"], R.thin(P, r))
 
 
-@pytest.mark.parametrize("name", ["clouds", "ties", "far", "one", "empty", "scales"])
+@pytest.mark.parametrize("name", ["clouds", "ties", "far", "one", "empty", "scales", "groups"])
 def test_nearest_is_exact(name, tmp_path):
     Q, S = nn_case(name)
     res = _emulate("nn:" + name, tmp_path)
@@ -294,7 +296,7 @@ def test_nearest_is_exact(name, tmp_path):
     db, ib = R.nearest_brute(Q[pick], S)
     assert np.array_equal(bits(res["dist"][pick]), bits(db))
     assert np.array_equal(res["idx"][pick], ib), "not the smallest index of the minimisers"
-    if name in ("clouds", "far", "scales"):              # unique minima: the kd-tree's index as well
+    if name in ("clouds", "far", "scales", "groups"):    # unique minima: the kd-tree's index as well
         assert np.array_equal(res["idx"], i)
     if name == "clouds":
         st = json.loads(str(res["stats"]))
