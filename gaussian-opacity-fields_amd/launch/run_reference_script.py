@@ -43,7 +43,16 @@ What it does, in this order (nothing in the reference checkout is edited):
      projection of all vertices into all views and the mesh container: the script's `cull_mesh` becomes mesh_cull.cull_mesh (the HIP
      mesh culling, csrc/mesh_cull.hip), and where cv2 / trimesh are not installed its `load_dtu_camera` becomes
      mesh_cull.load_dtu_camera and its `trimesh` a namespace whose load() is mesh_cull.load; import stand-ins for the packages that
-     are missing (shims_dtu/) go LAST on sys.path, for this script only.  GOF_DTU_CULL_TORCH=1 leaves the script alone.
+     are missing (shims_dtu/) go LAST on sys.path -- skimage's and cv2's for this script only, trimesh's for every script (10.).
+     GOF_DTU_CULL_TORCH=1 leaves the script alone.
+ 10. extract_mesh.py:36-120 and scene/gaussian_model.py:31-72, 433-463 ask torch einsums over views x points, boolean-mask assignments
+     and trimesh for the tetrahedralization's input points, the 8 bisection rounds and the mesh: GaussianModel.get_tetra_points
+     becomes mesh_extraction.get_tetra_points and the script's `marching_tetrahedra_with_binary_search` the function of that name in
+     mesh_extraction (csrc/extract.hip: one launch over candidates x views, one launch per round, a mesh_cull.DeviceMesh exported from
+     the device); the bound function queries the field through whatever `evaluage_alpha` is in the script's namespace when it is
+     called, so 6.'s switch still selects the script's own loop.  GOF_TORCH_EXTRACT=1 leaves both names alone.  `import trimesh`
+     (scene/gaussian_model.py:23, extract_mesh.py:12) resolves to the stand-in of shims_dtu/ where trimesh is not installed, for
+     every script; an installed trimesh wins.
 """
 import importlib
 import os
@@ -247,6 +256,60 @@ def add_dtu_shims(script):
             sys.path.append(shim)
 
 
+def add_trimesh_stand_in():
+    """for every script: scene/gaussian_model.py:23 and extract_mesh.py:12 import trimesh at module top, and with 10. nothing of it is
+    called -- where it is not installed its import stand-in goes LAST on sys.path (an installed trimesh wins)"""
+    shim = os.path.join(PKG, "shims_dtu", "trimesh")
+    if not _importable("trimesh") and shim not in sys.path:
+        sys.path.append(shim)
+
+
+def _torch_extract():
+    return os.environ.get("GOF_TORCH_EXTRACT", "0") == "1"
+
+
+def _get_tetra_points(self, views, near=0.02, far=1e6):
+    import mesh_extraction
+    return mesh_extraction.get_tetra_points(self, views, near, far)
+
+
+def rebind_tetra_points():
+    """GaussianModel.get_tetra_points (scene/gaussian_model.py:433-463) -> mesh_extraction.get_tetra_points, by name.  The replacement
+    imports mesh_extraction when it is called, not here (a script that never extracts a mesh does not load it)."""
+    if _torch_extract():
+        return
+    try:
+        from scene.gaussian_model import GaussianModel
+    except Exception:
+        return
+    GaussianModel.get_tetra_points = _get_tetra_points
+
+
+def _fused_evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color=False):
+    import mesh_extraction
+    return mesh_extraction.evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color)
+
+
+def _marching_tetrahedra_with_binary_search(model_path, name, iteration, views, gaussians, pipeline, background, kernel_size, filter_mesh,
+                                            texture_mesh, near, far):
+    """extract_mesh.py:36-120 -> mesh_extraction's, with the field queried through the `evaluage_alpha` of the script's namespace as it
+    is bound when this is called (the launcher's own fused loop: mesh_extraction reads the transmittance directly)"""
+    import mesh_extraction
+    query = getattr(sys.modules.get("__main__"), "evaluage_alpha", None)
+    if query is _fused_evaluate_alpha:
+        query = None
+    return mesh_extraction.marching_tetrahedra_with_binary_search(model_path, name, iteration, views, gaussians, pipeline, background, kernel_size,
+                                                                  filter_mesh, texture_mesh, near, far, evaluate_alpha=query)
+
+
+def extract_rebinding(script):
+    """the names to replace in `script`'s namespace for the mesh extraction: `marching_tetrahedra_with_binary_search` for every script
+    that defines it (extract_mesh.py), whether or not trimesh is importable; GOF_TORCH_EXTRACT=1: none"""
+    if _torch_extract():
+        return {}
+    return {"marching_tetrahedra_with_binary_search": _marching_tetrahedra_with_binary_search}
+
+
 def _tnt_eval_main(argv):
     import tnt_eval
     return tnt_eval.main(argv)
@@ -285,6 +348,7 @@ def main():
             if shim not in sys.path:
                 sys.path.append(shim)
     add_dtu_shims(script)
+    add_trimesh_stand_in()
     import diff_gaussian_rasterization  # noqa: F401  fail early and loudly if libgof_hip.so is missing
     if os.environ.get("GOF_STATS_JSON"):
         # the binding's counters of the whole run (frames redone for a pool / capacity learnt too small, read-backs, shapes that inherited
@@ -310,15 +374,15 @@ def main():
         pass
     if os.environ.get("GOF_TORCH_EPILOGUE", "0") != "1":
         rebind_train_epilogue()
+    rebind_tetra_points()
     if os.environ.get("GOF_INTEGRATE_CACHE_GB", "") not in ("0", "0.0"):
         rebind_integrate_with_view_cache()
     sys.argv = [script] + sys.argv[2:]
     rebind = {}
     if os.environ.get("GOF_TORCH_VIEW_REDUCE", "0") != "1":
         # extract_mesh.py:17-34: the script's own view loop -> the one whose min / arg-min reduction is fused into the point pass
-        import mesh_extraction
-        rebind["evaluage_alpha"] = lambda points, views, gaussians, pipeline, background, kernel_size, return_color=False: \
-            mesh_extraction.evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color)
+        rebind["evaluage_alpha"] = _fused_evaluate_alpha
+    rebind.update(extract_rebinding(script))
     # extract_mesh_tsdf.py:16-83: the script's Open3D VoxelBlockGrid loop -> the HIP TSDF fusion (csrc/tsdf.hip)
     import tsdf_fusion
     rebind["tsdf_fusion"] = tsdf_fusion.tsdf_fusion

@@ -200,16 +200,42 @@ class DeviceMesh:
 
     def __init__(self, vertices, faces, normals=None, colors=None, device=None):
         self.device = torch.device(device) if device is not None else _device()
-        self._v = self._up(np.ascontiguousarray(vertices, np.float64).reshape(-1, 3))
-        self._f = self._up(np.ascontiguousarray(faces, np.int32).reshape(-1, 3))
-        self._n = self._c = None
-        n = int(self._v.size(0))
-        if normals is not None:
-            self._n = self._up(np.ascontiguousarray(normals, np.float32).reshape(n, 3))
+        v = np.ascontiguousarray(vertices, np.float64).reshape(-1, 3)
+        n = len(v)
+        c = None
         if colors is not None:
             c = np.zeros((n, 4), np.uint8)
             c[:, :3] = np.asarray(colors, np.uint8).reshape(n, -1)[:, :3]
-            self._c = self._up(c)
+        self._set_tensors(self._up(v), self._up(np.ascontiguousarray(faces, np.int32).reshape(-1, 3)),
+                          None if normals is None else self._up(np.ascontiguousarray(normals, np.float32).reshape(n, 3)),
+                          None if c is None else self._up(c))
+
+    def _set_tensors(self, v, f, n, c):
+        """the one place the fields are set: fp64 (N,3), int32 (M,3), float32 (N,3) or None, uint8 (N,4) or None, on self.device"""
+        self._v, self._f, self._n, self._c = v, f, n, c
+
+    @classmethod
+    def from_device(cls, vertices, faces, normals=None, colors=None):
+        """A mesh over tensors that are on a ROCm device already, with no host round trip: vertices (N,3) float32 or float64, faces
+        (M,3) int32 or int64, optional normals (N,3) float32 and colours (N,3) or (N,4) uint8 (red green blue first)."""
+        v = _tensor(vertices, "DeviceMesh.from_device", "vertices", (torch.float32, torch.float64), 3)
+        f = _tensor(faces, "DeviceMesh.from_device", "faces", (torch.int32, torch.int64), 3)
+        n = int(v.size(0))
+        nrm = col = None
+        if normals is not None:
+            nrm = _tensor(normals, "DeviceMesh.from_device", "normals", (torch.float32,), 3)
+        if colors is not None:
+            c = _tensor(colors, "DeviceMesh.from_device", "colors", (torch.uint8,))
+            if c.dim() != 2 or c.size(1) not in (3, 4):
+                raise RuntimeError("DeviceMesh.from_device: colors must have dimensions (N, 3) or (N, 4)")
+            col = torch.cat([c[:, :3], torch.zeros((int(c.size(0)), 1), dtype=torch.uint8, device=c.device)], dim=1).contiguous()
+        for a, rows in ((f, None), (nrm, n), (col, n)):
+            if a is not None and (a.device != v.device or (rows is not None and a.size(0) != rows)):
+                raise RuntimeError("DeviceMesh.from_device: every tensor must be on the vertices' device, attributes with one row per vertex")
+        mesh = cls.__new__(cls)                               # (no host arrays to upload: __init__'s other half, the same setter)
+        mesh.device = v.device
+        mesh._set_tensors(v.to(torch.float64), f.to(torch.int32), nrm, col)
+        return mesh
 
     def _up(self, a):
         return torch.from_numpy(a).to(self.device)
@@ -260,6 +286,11 @@ class DeviceMesh:
         out = compact_mesh(keep_u8, self._f, self._attrs(), drop_faces=drop_faces)
         self._set_attrs(out["attrs"])
         self._f = out["faces"].contiguous()
+
+    def compact(self, keep):
+        """keep the vertices with keep[i] (bool or uint8, (N,)) and the faces between them, renumbered: update_vertices(keep) followed
+        by update_faces(keep[faces].all(1)) in one compaction"""
+        self._apply(self._mask(keep, int(self._v.size(0)), "compact"), True)
 
     def update_vertices(self, mask):
         """trimesh's: keep vertices[mask] and renumber the faces (the index of a removed vertex becomes 0: update_faces removes those)"""
@@ -344,7 +375,7 @@ def cull_mesh(cameras, mesh, radius=6):
             off += n
         if isinstance(mesh, DeviceMesh):
             keep = cull_vertices(mesh._v.float(), views)
-            mesh._apply(keep.view(torch.uint8), True)
+            mesh.compact(keep)
             return mesh
         v32 = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.vertices), np.float32).reshape(-1, 3)).to(dev)
         f32 = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.faces), np.int32).reshape(-1, 3)).to(dev)
