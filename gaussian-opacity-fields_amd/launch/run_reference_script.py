@@ -53,6 +53,11 @@ What it does, in this order (nothing in the reference checkout is edited):
      called, so 6.'s switch still selects the script's own loop.  GOF_TORCH_EXTRACT=1 leaves both names alone.  `import trimesh`
      (scene/gaussian_model.py:23, extract_mesh.py:12) resolves to the stand-in of shims_dtu/ where trimesh is not installed, for
      every script; an installed trimesh wins.
+ 11. render.py:18,35-36 and metrics.py:16,19,33-34,76,100 ask torchvision for save_image / to_tensor and the lpips package for
+     `lpips.LPIPS(net='vgg')`: where they are not installed, `import torchvision` and `import lpips` resolve to the stand-ins of
+     shims/ (LAST on sys.path: an installed package wins).  lpips.LPIPS is image_metrics.LPIPS (the HIP VGG16 feature distance,
+     csrc/lpips.hip); it reads the user's own weight files (GOF_LPIPS_VGG16, GOF_LPIPS_LIN, torch's hub cache, an installed lpips
+     package) and never downloads.  metrics.py's `ssim` is 4.'s.
 """
 import importlib
 import os
@@ -264,6 +269,27 @@ def add_trimesh_stand_in():
         sys.path.append(shim)
 
 
+def add_import_stand_ins():
+    """shims/ goes LAST on sys.path when one of the packages it stands in for is not importable: tetranerf and open3d (2., 6.), and
+    lpips and torchvision (11.).  An installed package comes earlier on the path and wins; lpips is looked up without importing it
+    (the real package imports torchvision's models at import)."""
+    import importlib.util
+    shim = os.path.join(PKG, "shims")
+    missing = False
+    for mod in ("tetranerf.utils.extension", "open3d"):
+        try:
+            importlib.import_module(mod)
+        except Exception:
+            missing = True
+    for mod in ("lpips", "torchvision"):
+        try:
+            missing = missing or importlib.util.find_spec(mod) is None
+        except (ImportError, ValueError):
+            missing = True
+    if missing and shim not in sys.path:
+        sys.path.append(shim)
+
+
 def _torch_extract():
     return os.environ.get("GOF_TORCH_EXTRACT", "0") == "1"
 
@@ -340,13 +366,7 @@ def main():
     ref_root = os.path.dirname(script)
     sys.path.insert(0, ref_root)
     sys.path.insert(0, PKG)
-    for mod in ("tetranerf.utils.extension", "open3d"):
-        try:
-            importlib.import_module(mod)
-        except Exception:
-            shim = os.path.join(PKG, "shims")
-            if shim not in sys.path:
-                sys.path.append(shim)
+    add_import_stand_ins()
     add_dtu_shims(script)
     add_trimesh_stand_in()
     import diff_gaussian_rasterization  # noqa: F401  fail early and loudly if libgof_hip.so is missing
