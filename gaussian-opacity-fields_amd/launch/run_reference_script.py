@@ -58,6 +58,11 @@ What it does, in this order (nothing in the reference checkout is edited):
      shims/ (LAST on sys.path: an installed package wins).  lpips.LPIPS is image_metrics.LPIPS (the HIP VGG16 feature distance,
      csrc/lpips.hip); it reads the user's own weight files (GOF_LPIPS_VGG16, GOF_LPIPS_LIN, torch's hub cache, an installed lpips
      package) and never downloads.  metrics.py's `ssim` is 4.'s.
+ 12. train.py:67-88 defines L1_loss_appearance (`--use_decoupled_appearance`: the reference's TNT and DTU runs) from torch convolutions,
+     pixel-shuffles and bilinear resamplings: with GOF_HIP_APPEARANCE=1 the script's name becomes
+     train_epilogue.appearance.L1_loss_appearance (csrc/appearance.hip: the network forward and backward on the exact fp32 matrix
+     instruction in fixed orders, bit-reproducible), rebound as 6. rebinds `evaluage_alpha`.  The network module, its optimizer groups
+     and checkpoints are the reference's.  GOF_TORCH_APPEARANCE=1 keeps the script's own function whatever else is set.
 """
 import importlib
 import os
@@ -336,6 +341,27 @@ def extract_rebinding(script):
     return {"marching_tetrahedra_with_binary_search": _marching_tetrahedra_with_binary_search}
 
 
+# Whether train.py's L1_loss_appearance is rebound without being asked for: decided by the measured iteration time (DESIGN.md §5,
+# profiles/appearance_timing.md).  The HIP path is bit-reproducible; it is the default only where it is no slower than torch's.
+APPEARANCE_BY_DEFAULT = False
+
+
+def _l1_loss_appearance(image, gt_image, gaussians, view_idx, return_transformed_image=False):
+    from train_epilogue import appearance
+    return appearance.L1_loss_appearance(image, gt_image, gaussians, view_idx, return_transformed_image)
+
+
+def appearance_rebinding(script):
+    """the names to replace in `script`'s namespace for the decoupled-appearance L1 (train.py:67-88): `L1_loss_appearance` for every
+    script that defines it.  GOF_TORCH_APPEARANCE=1 (or GOF_TORCH_EPILOGUE=1) keeps the script's own function; while the HIP path is not
+    the default, GOF_HIP_APPEARANCE=1 asks for it.  The replacement imports train_epilogue.appearance when it is called, not here."""
+    if os.environ.get("GOF_TORCH_APPEARANCE", "0") == "1" or os.environ.get("GOF_TORCH_EPILOGUE", "0") == "1":
+        return {}
+    if not APPEARANCE_BY_DEFAULT and os.environ.get("GOF_HIP_APPEARANCE", "0") != "1":
+        return {}
+    return {"L1_loss_appearance": _l1_loss_appearance}
+
+
 def _tnt_eval_main(argv):
     import tnt_eval
     return tnt_eval.main(argv)
@@ -383,6 +409,9 @@ def main():
                 d = sys.modules.get("train_epilogue.deferred")
                 if d is not None:                       # how many iterations' losses were one fused call / fell back to the eager mirrors
                     st["deferred_loss"] = dict(d.stats)
+                ap = sys.modules.get("train_epilogue.appearance")
+                if ap is not None:                      # how many appearance L1s ran on the HIP unit (12.)
+                    st["appearance"] = dict(ap.stats)
                 with open(path, "w") as f:
                     json.dump(st, f)
         atexit.register(_dump_stats)
@@ -408,6 +437,7 @@ def main():
     rebind["tsdf_fusion"] = tsdf_fusion.tsdf_fusion
     rebind.update(dtu_eval_rebinding(script))
     rebind.update(dtu_cull_rebinding(script))
+    rebind.update(appearance_rebinding(script))
     run_script(script, rebind)
 
 

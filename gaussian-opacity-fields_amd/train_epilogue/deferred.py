@@ -18,7 +18,7 @@ keeps the eager mirrors) those hand back DEFERRED values:
                                 the rasterizer's backward; .item() afterwards reads the terms that call left
 
     + / - a 0-dim tensor        carried along as it is (its own autograd graph): the decoupled-appearance L1 of train.py:158-159 -- the
-                                reference's TNT / DTU runs -- goes through a network and stays torch code; `0.8 * that + 0.2 * (1 - ssim)`
+                                reference's TNT / DTU runs -- goes through a network (torch's, or appearance.py's on HIP); `0.8 * that + 0.2 * (1 - ssim)`
                                 keeps the rest deferred, and loss.backward() starts ONE pass from the fused gradient and from the tensor
 
 ANY other use of a deferred object -- an operator, torch function, attribute or argument pattern not listed above, a different
@@ -222,7 +222,7 @@ def _is_scalar_tensor(x):
 
 class DeferredLoss(_Deferred):
     """sum_i coef[i] * term_i + const (+ extra) over the terms "l1", "ssim", "dn", "dist" of one frame (train.py:156-182).  `extra`: a 0-dim
-    TENSOR the script added -- the decoupled-appearance L1 of train.py:158-159, which goes through a network and stays torch code -- carried
+    TENSOR the script added -- the decoupled-appearance L1 of train.py:158-159, which goes through a network (appearance.py) -- carried
     along as it is (its own autograd graph): the deferred part is still one fused call, and the backward starts from both."""
     def __init__(self, frame, coef, const, extra=None):
         self.frame, self.coef, self.const, self.extra = frame, coef, const, extra

@@ -73,7 +73,7 @@ int gof_l1_backward(uint64_t n, const float* a, const float* b, const float* gra
  *          depth_normal = depth_to_normal(view, rendering[6]); render_normal = normalize(rendering[3:6], dim=0)
  *          depth_normal_loss = mean(1 - <c2w[:3,:3] @ render_normal, depth_normal>)                               :170-182
  *          loss = rgb_loss + depth_normal_loss l_dn + distortion_loss l_dist                                      :188
- *      (the decoupled-appearance variant of Ll1, :158-159, goes through a network and stays torch code).
+ *      (the decoupled-appearance variant of Ll1, :158-159, goes through a network: gof_appearance_hip.h, not part of this call).
  *      rendering [9,H,W] is the rasterizer's output, gt_image [3,H,W].  terms (device, 6 floats) receives
  *      {loss, Ll1, ssim, rgb_loss, depth_normal_loss, distortion_loss}; dL_drendering [9,H,W] (nullable: values only) receives
  *      d loss / d rendering, every element written.  Five launches, sums in a fixed order (deterministic).
