@@ -15,6 +15,7 @@
 #include "../../include/gof_hip.h"
 #include "../../include/gof_train_hip.h"
 #include "gof_common.h"
+#include "gof_activations.h"
 #include "radix.h"
 
 namespace gof {
@@ -116,7 +117,7 @@ act_scaling_fwd(int64_t P, const float* __restrict__ rs, const float* __restrict
     if (i >= P) return;
     const float f = f3[i], ff = f * f;                          // torch.square(self.filter_3D)
 #pragma unroll
-    for (int c = 0; c < 3; c++) { const float s = expf(rs[3 * i + c]); out[3 * i + c] = sqrtf(s * s + ff); }     // :160-161
+    for (int c = 0; c < 3; c++) out[3 * i + c] = act_scaling_value(rs[3 * i + c], ff);                           // :160-161
 }
 __global__ void __launch_bounds__(256)
 act_scaling_bwd(int64_t P, const float* __restrict__ rs, const float* __restrict__ f3, const float* g, float* grs)      // grs may alias g (in-place, activations.INPLACE_GRAD)
@@ -138,13 +139,7 @@ act_opacity_fwd(int64_t P, const float* __restrict__ ro, const float* __restrict
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
     const float f = f3[i], ff = f * f;
-    const float s0 = expf(rs[3 * i]), s1 = expf(rs[3 * i + 1]), s2 = expf(rs[3 * i + 2]);
-    const float q0 = s0 * s0, q1 = s1 * s1, q2 = s2 * s2;       // scales_square (:188)
-    const float det1 = q0 * q1 * q2;                            // :189
-    const float det2 = (q0 + ff) * (q1 + ff) * (q2 + ff);       // :191-192
-    const float coef = sqrtf(det1 / det2);                      // :193
-    const float o = 1.0f / (1.0f + expf(-ro[i]));               // sigmoid
-    out[i] = o * coef;                                          // :194
+    out[i] = act_opacity_value(ro[i], rs[3 * i], rs[3 * i + 1], rs[3 * i + 2], ff);      // :184-194 (gof_activations.h)
 }
 __global__ void __launch_bounds__(256)
 act_opacity_bwd(int64_t P, const float* __restrict__ ro, const float* __restrict__ rs, const float* __restrict__ f3, const float* g,

@@ -63,6 +63,14 @@ What it does, in this order (nothing in the reference checkout is edited):
      train_epilogue.appearance.L1_loss_appearance (csrc/appearance.hip: the network forward and backward on the exact fp32 matrix
      instruction in fixed orders, bit-reproducible), rebound as 6. rebinds `evaluage_alpha`.  The network module, its optimizer groups
      and checkpoints are the reference's.  GOF_TORCH_APPEARANCE=1 keeps the script's own function whatever else is set.
+ 13. scene/gaussian_model.py:390-430, 486-530 move the model between its tensors and point_cloud.ply through plyfile: eight
+     device-to-host copies, a concatenation and one Python tuple per Gaussian (train.py saves through it, render.py, extract_mesh.py,
+     extract_mesh_tsdf.py and create_fused_ply.py load through it): GaussianModel.save_ply / save_fused_ply / load_ply become model_io's
+     (csrc/model_io.hip: the row transpose on the device, in front of one pinned copy per chunk of rows), by name; the reference's own
+     methods are kept and serve a model that is not on the device.  GOF_TORCH_PLY=1 leaves the three methods alone.  `import plyfile`
+     (scene/gaussian_model.py:18, scene/dataset_readers.py:22: fetchPly / storePly still go through it) resolves to the stand-in of
+     shims/ where plyfile is not installed, and `import cv2` (train.py:15, nothing of it is called) to the one of shims_dtu/ for every
+     script; an installed package wins.
 """
 import importlib
 import os
@@ -274,10 +282,18 @@ def add_trimesh_stand_in():
         sys.path.append(shim)
 
 
+def add_cv2_stand_in():
+    """for every script: train.py:15 imports cv2 at module top and calls nothing of it -- where it is not installed its import stand-in
+    goes LAST on sys.path (an installed cv2 wins)"""
+    shim = os.path.join(PKG, "shims_dtu", "cv2")
+    if not _importable("cv2") and shim not in sys.path:
+        sys.path.append(shim)
+
+
 def add_import_stand_ins():
-    """shims/ goes LAST on sys.path when one of the packages it stands in for is not importable: tetranerf and open3d (2., 6.), and
-    lpips and torchvision (11.).  An installed package comes earlier on the path and wins; lpips is looked up without importing it
-    (the real package imports torchvision's models at import)."""
+    """shims/ goes LAST on sys.path when one of the packages it stands in for is not importable: tetranerf and open3d (2., 6.),
+    lpips and torchvision (11.) and plyfile (13.).  An installed package comes earlier on the path and wins; lpips and plyfile are
+    looked up without importing them (the real lpips imports torchvision's models at import)."""
     import importlib.util
     shim = os.path.join(PKG, "shims")
     missing = False
@@ -286,7 +302,7 @@ def add_import_stand_ins():
             importlib.import_module(mod)
         except Exception:
             missing = True
-    for mod in ("lpips", "torchvision"):
+    for mod in ("lpips", "torchvision", "plyfile"):
         try:
             missing = missing or importlib.util.find_spec(mod) is None
         except (ImportError, ValueError):
@@ -314,6 +330,46 @@ def rebind_tetra_points():
     except Exception:
         return
     GaussianModel.get_tetra_points = _get_tetra_points
+
+
+# the reference's own save_ply / save_fused_ply / load_ply as they were when rebind_model_io replaced them: model_io calls them for a
+# model that is not float32 on a ROCm device
+_REFERENCE_PLY = {}
+
+
+def _model_io():
+    import model_io
+    model_io.reference = _REFERENCE_PLY
+    return model_io
+
+
+def _save_ply(self, path):
+    return _model_io().save_ply(self, path)
+
+
+def _save_fused_ply(self, path):
+    return _model_io().save_fused_ply(self, path)
+
+
+def _load_ply(self, path):
+    return _model_io().load_ply(self, path)
+
+
+def rebind_model_io():
+    """GaussianModel.save_ply / save_fused_ply / load_ply (scene/gaussian_model.py:390-430, 486-530) -> model_io's, by name.  The
+    replacements import model_io when they are called, not here; GOF_TORCH_PLY=1 leaves the reference's methods in place."""
+    if os.environ.get("GOF_TORCH_PLY", "0") == "1":
+        return
+    try:
+        from scene.gaussian_model import GaussianModel
+    except Exception:
+        return
+    for name, new in (("save_ply", _save_ply), ("save_fused_ply", _save_fused_ply), ("load_ply", _load_ply)):
+        current = getattr(GaussianModel, name, None)
+        if current is None or current is new:
+            continue
+        _REFERENCE_PLY[name] = current
+        setattr(GaussianModel, name, new)
 
 
 def _fused_evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color=False):
@@ -395,6 +451,7 @@ def main():
     add_import_stand_ins()
     add_dtu_shims(script)
     add_trimesh_stand_in()
+    add_cv2_stand_in()
     import diff_gaussian_rasterization  # noqa: F401  fail early and loudly if libgof_hip.so is missing
     if os.environ.get("GOF_STATS_JSON"):
         # the binding's counters of the whole run (frames redone for a pool / capacity learnt too small, read-backs, shapes that inherited
@@ -424,6 +481,7 @@ def main():
     if os.environ.get("GOF_TORCH_EPILOGUE", "0") != "1":
         rebind_train_epilogue()
     rebind_tetra_points()
+    rebind_model_io()
     if os.environ.get("GOF_INTEGRATE_CACHE_GB", "") not in ("0", "0.0"):
         rebind_integrate_with_view_cache()
     sys.argv = [script] + sys.argv[2:]
