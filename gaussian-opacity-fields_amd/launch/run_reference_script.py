@@ -71,6 +71,15 @@ What it does, in this order (nothing in the reference checkout is edited):
      (scene/gaussian_model.py:18, scene/dataset_readers.py:22: fetchPly / storePly still go through it) resolves to the stand-in of
      shims/ where plyfile is not installed, and `import cv2` (train.py:15, nothing of it is called) to the one of shims_dtu/ for every
      script; an installed package wins.
+ 14. utils/camera_utils.py:19-62 builds the scene's cameras in a serial loop: Pillow decodes and resizes each image on one CPU thread,
+     np.array(...) / 255.0 turns 3 bytes per pixel into 12 and the float tensor is uploaded from pageable memory: loadCam and
+     cameraList_from_camInfos become scene_images' (csrc/scene_images.hip: Pillow's bicubic resampler and the conversion to float planes
+     on the device, bit for bit; worker threads decode ahead, the raw bytes travel through two pinned buffers), by name, in
+     utils.camera_utils and in `scene` (scene/__init__.py:19 takes cameraList_from_camInfos by name, and the two modules import each
+     other, so `scene` is imported first and its name rebound too).  The reference's own functions are kept and serve an
+     image whose mode is not RGB, RGBA or L.  The output is bit-identical; the loading time has not been measured on the device yet, so
+     the binding is asked for with GOF_HIP_IMAGES=1 (SCENE_IMAGES_BY_DEFAULT below) and GOF_PIL_IMAGES=1 leaves both functions alone
+     whatever else is set; GOF_IMAGE_DECODE_THREADS (default 8, 1..16) sizes the decoding pool.
 """
 import importlib
 import os
@@ -372,6 +381,57 @@ def rebind_model_io():
         setattr(GaussianModel, name, new)
 
 
+# the reference's own loadCam / cameraList_from_camInfos as they were when rebind_scene_images replaced them: scene_images calls loadCam
+# for an image mode the resampler does not take
+_REFERENCE_IMAGES = {}
+
+
+def _scene_images():
+    import scene_images
+    scene_images.reference = _REFERENCE_IMAGES
+    return scene_images
+
+
+def _load_cam(args, id, cam_info, resolution_scale):
+    return _scene_images().load_cam(args, id, cam_info, resolution_scale)
+
+
+def _camera_list_from_cam_infos(cam_infos, resolution_scale, args):
+    return _scene_images().camera_list_from_cam_infos(cam_infos, resolution_scale, args)
+
+
+# Whether the two functions are rebound without being asked for: decided by the measured loading time (profiles/scene_images_timing.md;
+# tests/devtools/dev_scene_images.py measures it).  The output is bit-identical either way; the binding becomes the default once the
+# new loader has been shown faster than the reference's at both sizes of that record.  Until then GOF_HIP_IMAGES=1 asks for it.
+SCENE_IMAGES_BY_DEFAULT = False
+
+
+def rebind_scene_images():
+    """utils.camera_utils.loadCam / cameraList_from_camInfos (utils/camera_utils.py:19-62) -> scene_images', by name.  The reference's
+    utils.camera_utils imports scene.cameras and scene/__init__.py:19 takes cameraList_from_camInfos from it by name -- a cycle that only
+    resolves when `scene` is imported first -- so `scene` is imported here and the name in ITS namespace (the one Scene.__init__ calls)
+    is rebound together with the two in utils.camera_utils.  The replacements import scene_images when they are called, not here;
+    GOF_PIL_IMAGES=1 leaves the reference's functions in place whatever else is set; while the binding is not the default,
+    GOF_HIP_IMAGES=1 asks for it."""
+    if os.environ.get("GOF_PIL_IMAGES", "0") == "1":
+        return
+    if not SCENE_IMAGES_BY_DEFAULT and os.environ.get("GOF_HIP_IMAGES", "0") != "1":
+        return
+    try:
+        import scene as ref_scene
+        import utils.camera_utils as cu
+    except Exception:
+        return
+    for name, new in (("loadCam", _load_cam), ("cameraList_from_camInfos", _camera_list_from_cam_infos)):
+        current = getattr(cu, name, None)
+        if current is None or current is new:
+            continue
+        _REFERENCE_IMAGES[name] = current
+        setattr(cu, name, new)
+        if getattr(ref_scene, name, None) is current:
+            setattr(ref_scene, name, new)
+
+
 def _fused_evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color=False):
     import mesh_extraction
     return mesh_extraction.evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color)
@@ -482,6 +542,7 @@ def main():
         rebind_train_epilogue()
     rebind_tetra_points()
     rebind_model_io()
+    rebind_scene_images()
     if os.environ.get("GOF_INTEGRATE_CACHE_GB", "") not in ("0", "0.0"):
         rebind_integrate_with_view_cache()
     sys.argv = [script] + sys.argv[2:]
