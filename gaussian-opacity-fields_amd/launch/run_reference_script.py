@@ -80,6 +80,15 @@ What it does, in this order (nothing in the reference checkout is edited):
      image whose mode is not RGB, RGBA or L.  The output is bit-identical; the loading time has not been measured on the device yet, so
      the binding is asked for with GOF_HIP_IMAGES=1 (SCENE_IMAGES_BY_DEFAULT below) and GOF_PIL_IMAGES=1 leaves both functions alone
      whatever else is set; GOF_IMAGE_DECODE_THREADS (default 8, 1..16) sizes the decoding pool.
+ 15. render.py:35-36 saves two PNG files per view through torchvision.utils.save_image: a blocking copy to the host and Pillow's encoder on
+     one CPU thread, next to a render of a few milliseconds.  With GOF_HIP_PNG=1 `torchvision.utils.save_image` (the stand-in's of 11. or an
+     installed torchvision's: render.py reaches it by attribute) becomes image_writer.save_image before the script runs
+     (csrc/png_encode.hip: quantisation, PNG filters, deflate and Adler-32 on the device; one writer thread frames and writes the files
+     behind a ring of pinned buffers, so the render loop does not synchronise per image).  The files are valid PNGs with identical pixels,
+     not Pillow's bytes.  Anything that is not a float32 image of 1 or 3 channels going to a .png file name (train.py:235's jpg, file
+     objects) goes to the function that was bound before.  image_writer.flush() runs after the script's __main__ returns or raises (and at
+     exit): an error of the writer thread surfaces there.  Its speed has not been measured on the device yet, so the binding is asked for
+     (PNG_WRITER_BY_DEFAULT below); GOF_PIL_PNG=1 leaves the function alone whatever else is set.
 """
 import importlib
 import os
@@ -432,6 +441,51 @@ def rebind_scene_images():
             setattr(ref_scene, name, new)
 
 
+# what torchvision.utils.save_image was when rebind_png_writer replaced it: image_writer calls it for everything but a PNG file of a
+# float32 image with 1 or 3 channels
+_PREVIOUS_SAVE_IMAGE = {}
+
+# Whether save_image is rebound without being asked for: decided by the measured time of render.py's loop (profiles/png_encode.md;
+# tests/devtools/dev_png_encode.py measures it).  Until that record shows the device path faster at both sizes, GOF_HIP_PNG=1 asks for it.
+PNG_WRITER_BY_DEFAULT = False
+
+
+def _image_writer():
+    import image_writer
+    image_writer.previous = _PREVIOUS_SAVE_IMAGE.get("save_image")
+    return image_writer
+
+
+def _save_image(tensor, fp, format=None, **kwargs):
+    return _image_writer().save_image(tensor, fp, format=format, **kwargs)
+
+
+def rebind_png_writer():
+    """torchvision.utils.save_image (render.py:35-36) -> image_writer.save_image, by attribute of the module the script imports (the
+    stand-in of shims/ or an installed torchvision).  The replacement imports image_writer when it is called, not here; GOF_PIL_PNG=1
+    leaves the function in place whatever else is set; while the binding is not the default, GOF_HIP_PNG=1 asks for it."""
+    if os.environ.get("GOF_PIL_PNG", "0") == "1":
+        return
+    if not PNG_WRITER_BY_DEFAULT and os.environ.get("GOF_HIP_PNG", "0") != "1":
+        return
+    try:
+        import torchvision.utils as tvu
+    except Exception:
+        return
+    current = getattr(tvu, "save_image", None)
+    if current is None or current is _save_image:
+        return
+    _PREVIOUS_SAVE_IMAGE["save_image"] = current
+    tvu.save_image = _save_image
+
+
+def flush_png_writer():
+    """wait for the files image_writer still holds; re-raises the first error of its writer thread"""
+    iw = sys.modules.get("image_writer")
+    if iw is not None:
+        iw.flush()
+
+
 def _fused_evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color=False):
     import mesh_extraction
     return mesh_extraction.evaluate_alpha(points, views, gaussians, pipeline, background, kernel_size, return_color)
@@ -543,6 +597,7 @@ def main():
     rebind_tetra_points()
     rebind_model_io()
     rebind_scene_images()
+    rebind_png_writer()
     if os.environ.get("GOF_INTEGRATE_CACHE_GB", "") not in ("0", "0.0"):
         rebind_integrate_with_view_cache()
     sys.argv = [script] + sys.argv[2:]
@@ -557,7 +612,15 @@ def main():
     rebind.update(dtu_eval_rebinding(script))
     rebind.update(dtu_cull_rebinding(script))
     rebind.update(appearance_rebinding(script))
-    run_script(script, rebind)
+    try:
+        run_script(script, rebind)
+    except BaseException:
+        try:
+            flush_png_writer()                  # (the files queued before the script failed are still written; its own error is the one reported)
+        except Exception:
+            pass
+        raise
+    flush_png_writer()
 
 
 def _is_main_guard(node):
