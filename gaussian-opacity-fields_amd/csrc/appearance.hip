@@ -6,9 +6,9 @@
 // Arithmetic: compiled with -ffp-contract=off like the whole library; every fused multiply-add is written (fmaf) or is the matrix
 // instruction's own (mma_f32.h).  No floating-point atomics: every sum has a fixed order.
 //
-// The convolution is csrc/lpips.hip's kernel, generalised in a copy of its own (gof_lpips_* stay as they are): the pixel operand is
-// staged through fetch() (the views of the header), output channels that do not fill the tile are zero weight rows that are not
-// stored, the bias is optional.  Same tiles, same LDS layout, same order of K.
+// The convolution is the main loop of conv3x3_f32.h (the one csrc/lpips.hip runs: same tiles, same LDS layout, same order of K) on one
+// plane: the pixel operand is staged through fetch() (the views of the header), output channels that do not fill the tile are zero
+// weight rows that are not stored, the bias is optional, and conv3's epilogue is the head (sigmoid, product, L1 partial sums).
 //
 // The weight gradient.  GEMM view: M = C_out, N = 9 C_in + 1 (column n = ci * 9 + ky * 3 + kx; the last column is the constant 1:
 // the bias gradient), K = the pixels of one chunk.  A workgroup of 4 waves owns one chunk x 32 output channels x 128 columns (one
@@ -21,13 +21,11 @@
 #include "../../include/gof_appearance_hip.h"
 #include "gof_common.h"
 #include "gof_geom.h"
-#include "mma_f32.h"
+#include "conv3x3_f32.h"
 
 namespace gof {
 namespace app {
 
-constexpr int KC = 36;          // terms of a full K chunk of the convolution: 4 input channels x 9 taps
-constexpr int KP = 37;          // row pitch of its weight operand in LDS
 constexpr int WG_PS = 64;       // pixels per stage of the weight gradient
 constexpr int WG_PP = 65;       // row pitch of its operands in LDS
 constexpr int WG_BN = 128;      // columns per workgroup
@@ -166,111 +164,52 @@ materialize_kernel(int C, Src src, float* __restrict__ out)
 // =====================================================================================================================================
 // 3x3 convolution, zero padding 1 (+ bias) (+ ReLU): M = the pixels of the plane, N = C_out, K = 9 C_in
 // =====================================================================================================================================
+// pixel p of the view's plane, read through fetch()
+struct ViewOperand {
+    const Src& src;
+    int W, H, y, x;
+
+    __device__ __forceinline__ bool prepare(int p) { y = p / W; x = p - y * W; return p < H * W; }
+    __device__ __forceinline__ float load(int ci, int tap) const { return fetch(src, ci, y + tap / 3 - 1, x + tap % 3 - 1); }
+};
+
 template <int WN, int WGN>
 __global__ void __launch_bounds__(256)
 conv3x3_kernel(int C_in, int C_out, Src src, const float* __restrict__ w, const float* __restrict__ bias, int relu, float* __restrict__ out, Head head)
 {
-    constexpr int WGM = 4 / WGN, BM = 64 * WGM, BN = 32 * WN * WGN, BMP = BM + 32;
-    constexpr int RPT = KC * BM / 256;                     // X rows a thread stages per chunk (36 or 18: whole input channels)
-    __shared__ float Xs[KC * BMP];
-    __shared__ float Ws[BN * KP];
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int m0 = (int)blockIdx.x * BM, n0 = (int)blockIdx.y * BN;
-    const int W = src.W, H = src.H, M = H * W, K = 9 * C_in;
-
-    // the pixel this thread stages and which of its 9 taps lie inside the image
-    const int lm = t % BM, lk0 = t / BM;
-    const int p = m0 + lm;
-    int y = 0, xx = 0;
-    unsigned inside = 0;
-    if (p < M) {
-        y = p / W; xx = p - y * W;
-        for (int ky = 0; ky < 3; ky++)
-            for (int kx = 0; kx < 3; kx++)
-                if (y + ky - 1 >= 0 && y + ky - 1 < H && xx + kx - 1 >= 0 && xx + kx - 1 < W) inside |= 1u << (ky * 3 + kx);
-    }
-
-    const int wm_base = (wave % WGM) * 64, wn_base = (wave / WGM) * 32 * WN;
-    f32x16 acc[2][WN];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
-
-    for (int c0 = 0; c0 < C_in; c0 += 4) {
-        const int nci = (C_in - c0 < 4) ? C_in - c0 : 4;
-        const int klen = 9 * nci, kpad = (klen + 1) & ~1;
-        // pixel operand: rows kk = lk0 * RPT + j, all KC of them (rows behind klen are zeros: the pad term, and never NaN)
-#pragma unroll
-        for (int j = 0; j < RPT; j++) {
-            const int kk = lk0 * RPT + j;
-            const int ci = lk0 * (RPT / 9) + j / 9, tap = j % 9;
-            float v = 0.0f;
-            if (kk < klen && ((inside >> tap) & 1u)) v = fetch(src, c0 + ci, y + tap / 3 - 1, xx + tap % 3 - 1);
-            Xs[kk * BMP + lm] = v;
-        }
-        // weight operand: row n = 36 consecutive floats of the weight tensor; rows behind C_out are zeros
-        for (int e = t; e < BN * KC; e += 256) {
-            const int n = e / KC, kk = e - n * KC;
-            Ws[n * KP + kk] = (kk < klen && n0 + n < C_out) ? w[(size_t)(n0 + n) * (size_t)K + (size_t)(c0 * 9 + kk)] : 0.0f;
-        }
-        __syncthreads();
-        for (int ks = 0; ks < kpad; ks += 2) {
-            const int kk = ks + (lane >> 5);
-            float a[WN], b[2];
-#pragma unroll
-            for (int j = 0; j < WN; j++) a[j] = Ws[(wn_base + 32 * j + (lane & 31)) * KP + kk];
-#pragma unroll
-            for (int i = 0; i < 2; i++) b[i] = Xs[kk * BMP + wm_base + 32 * i + (lane & 31)];
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int j = 0; j < WN; j++) acc[i][j] = mma_32x32x2(a[j], b[i], acc[i][j]);
-        }
-        __syncthreads();
-    }
-
-    // conv3 of the appearance network: sigmoid, product with the image and the L1 partial sum in the epilogue; z is never stored.
-    // (host: only with C_out == 3 and the 256-pixel tile.)  Per workgroup: the three channels of a pixel are added in channel order,
-    // then the 256 pixels in the tree of block_sum_256, all in fp64.
-    if (head.on) {
-        __shared__ double s_val[256];
-        if (BM == 256) {
-            Xs[t] = 0.0f; Xs[BM + t] = 0.0f; Xs[2 * BM + t] = 0.0f;
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; i++) {
-                const int q = m0 + wm_base + 32 * i + (lane & 31);
-                if (q >= M || lane >= 32) continue;
-#pragma unroll
-                for (int r = 0; r < 3; r++) Xs[r * BM + (q - m0)] = head_element(head, acc[i][0][r] + bias[r], r, q);
+    const int M = src.H * src.W;
+    conv3x3::main_loop<WN, WGN, false>(C_in, C_out, ViewOperand{ src, src.W, src.H, 0, 0 }, w,
+        [&](const f32x16 (&acc)[2][WN], int m0, int n0, int wm_base, int wn_base, int lane, float* Xs) {
+            // conv3 of the appearance network: sigmoid, product with the image and the L1 partial sum in the epilogue; z is never stored.
+            // (host: only with C_out == 3 and the 256-pixel tile.)  Per workgroup: the three channels of a pixel are added in channel
+            // order, then the 256 pixels in the tree of block_sum_256, all in fp64.  Xs: the main loop's LDS, free by now.
+            if (head.on) {
+                __shared__ double s_val[256];
+                constexpr int BM = 256 / WGN;
+                if (BM == 256) {
+                    const int t = (int)threadIdx.x;
+                    Xs[t] = 0.0f; Xs[BM + t] = 0.0f; Xs[2 * BM + t] = 0.0f;
+                    __syncthreads();
+                    // (n0 = wn_base = 0 here, so co < 3 is tile (., 0), registers 0 - 2 of lanes 0 - 31: one lane holds a pixel's three channels)
+                    conv3x3::for_each_output<WN>(acc, M, m0, n0, wm_base, wn_base, lane, [&](int q) {
+                        return [&, q](int co, float v) { if (co < 3) Xs[co * BM + (q - m0)] = head_element(head, v + bias[co], co, q); };
+                    });
+                    __syncthreads();
+                    const double v = ((double)Xs[t] + (double)Xs[BM + t]) + (double)Xs[2 * BM + t];
+                    const double total = block_sum_256(v, s_val);
+                    if (t == 0) head.partial[blockIdx.x] = total;
+                }
+                return;
             }
-            __syncthreads();
-            const double v = ((double)Xs[t] + (double)Xs[BM + t]) + (double)Xs[2 * BM + t];
-            const double total = block_sum_256(v, s_val);
-            if (t == 0) head.partial[blockIdx.x] = total;
-        }
-        return;
-    }
-
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const int q = m0 + wm_base + 32 * i + (lane & 31);
-        if (q >= M) continue;
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int co = n0 + wn_base + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (co >= C_out) continue;
-                float v = acc[i][j][r];
-                if (bias) v = v + bias[co];
-                if (relu) v = (v < 0.0f) ? 0.0f : v;
-                out[(size_t)co * (size_t)M + (size_t)q] = v;
-            }
-    }
+            conv3x3::for_each_output<WN>(acc, M, m0, n0, wm_base, wn_base, lane, [&](int q) {
+                return [&, q](int co, float v) {
+                    if (co >= C_out) return;
+                    if (bias) v = v + bias[co];
+                    if (relu) v = (v < 0.0f) ? 0.0f : v;
+                    out[(size_t)co * (size_t)M + (size_t)q] = v;
+                };
+            });
+        });
 }
 
 // out [C_in][C_out][9] = w [C_out][C_in][8 - tap]
@@ -532,16 +471,11 @@ static int launch_conv(int c_in, int c_out, const Src& src, const float* w, cons
     Head head{};
     if (head_or_null) head = *head_or_null;       // (only with c_out == 3: the 256-pixel tile below)
     const int M = src.H * src.W;
-    if (c_out > 64) {
-        const dim3 grid((unsigned)((M + 127) / 128), (unsigned)((c_out + 127) / 128));
-        hipLaunchKernelGGL((conv3x3_kernel<2, 2>), grid, dim3(256), 0, stream, c_in, c_out, src, w, bias, relu, out, head);
-    } else if (c_out > 32) {
-        const dim3 grid((unsigned)((M + 255) / 256), 1u);
-        hipLaunchKernelGGL((conv3x3_kernel<2, 1>), grid, dim3(256), 0, stream, c_in, c_out, src, w, bias, relu, out, head);
-    } else {
-        const dim3 grid((unsigned)((M + 255) / 256), 1u);
-        hipLaunchKernelGGL((conv3x3_kernel<1, 1>), grid, dim3(256), 0, stream, c_in, c_out, src, w, bias, relu, out, head);
-    }
+#define GOF_LAUNCH_CONV(WN, WGN) hipLaunchKernelGGL((conv3x3_kernel<WN, WGN>), (conv3x3::grid<WN, WGN>(M, c_out)), dim3(256), 0, stream, c_in, c_out, src, w, bias, relu, out, head)
+    if (c_out > 64) GOF_LAUNCH_CONV(2, 2);
+    else if (c_out > 32) GOF_LAUNCH_CONV(2, 1);
+    else GOF_LAUNCH_CONV(1, 1);
+#undef GOF_LAUNCH_CONV
     GOF_LAUNCH_CHECK(stream, 0);
     return GOF_OK;
 }

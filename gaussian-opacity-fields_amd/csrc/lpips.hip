@@ -6,119 +6,58 @@
 // Arithmetic: compiled with -ffp-contract=off like the whole library; every fused multiply-add is written (fmaf) or is the matrix
 // instruction's own, which is bit for bit a k-ordered fmaf chain.  No floating-point atomics: every sum has a fixed order.
 //
-// The convolution.  GEMM view: M = pixels of all images, N = C_out, K = 9 C_in with k = ci * 9 + ky * 3 + kx (torch's flattening of
-// the weight, so the weight tensor is read as it lies).  A workgroup of 4 waves owns BM pixels x BN output channels and walks K in
-// chunks of 4 input channels (36 terms; the last chunk of a C_in that is no multiple of 4 is shorter and padded to an even length
-// with a term 0 * 0).  Per chunk the pixel operand X[k][m] (the shifted image values, 0 outside the image: the zero padding) and the
-// weight operand Wt[n][k] are staged in LDS, then every wave runs the chunk's k-steps on its 2 x WN accumulator tiles of 32 x 32.
-// The instruction takes the WEIGHTS in its A slot and the PIXELS in its B slot, i.e. it forms the transposed tile: an accumulator
-// register then holds 32 consecutive pixels of one output channel across lanes 0-31, and the planar output is stored in 128-byte rows.
-//   LDS: X [36][BM + 32] (the pad makes the two k rows a k-step reads fall into different bank halves), Wt [BN][37].
-//   C_out % 128 == 0: BM = 128, BN = 128 (waves 2 x 2);  C_out % 64 == 0: BM = 256, BN = 64;  C_out % 32 == 0: BM = 256, BN = 32.
+// The convolution is the main loop of conv3x3_f32.h (the GEMM view, the LDS layout and the order of K are written there) over a batch
+// [img][C][H][W]: M = the pixels of all images, so a tile may span an image boundary; bias and optional ReLU in the store.
+//   C_out % 128 == 0: tile <2, 2>;  C_out % 64 == 0: <2, 1>;  C_out % 32 == 0: <1, 1> -- every weight tile is full.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "../../include/gof_hip.h"
 #include "../../include/gof_lpips_hip.h"
 #include "gof_common.h"
 #include "gof_geom.h"
-#include "mma_f32.h"
+#include "conv3x3_f32.h"
 
 namespace gof {
 namespace lpips {
 
-// the matrix step mma_32x32x2 (one v_mfma_f32_32x32x2_f32; restated with fmaf for the CPU suite): mma_f32.h
-
-constexpr int KC = 36;          // terms of a full K chunk: 4 input channels x 9 taps
-constexpr int KP = 37;          // row pitch of the weight operand in LDS (odd: a wave's 32 rows fall into 32 banks)
-
 // =====================================================================================================================================
 // 3x3 convolution, zero padding 1, + bias (+ ReLU)
 // =====================================================================================================================================
+// pixel p of the batch: image p / HW, offset p % HW in each of its channel planes
+struct BatchOperand {
+    const float* __restrict__ in;
+    int M, C_in, W, H, HW, y, x;
+    size_t base;            // of the pixel this thread stages, in channel 0 of its image
+
+    __device__ __forceinline__ bool prepare(int p)
+    {
+        if (p >= M) return false;
+        const int img = p / HW, rem = p - img * HW;
+        y = rem / W; x = rem - y * W;
+        base = (size_t)img * (size_t)C_in * (size_t)HW + (size_t)rem;
+        return true;
+    }
+    __device__ __forceinline__ float load(int ci, int tap) const { return in[base + (size_t)ci * (size_t)HW + (size_t)((tap / 3 - 1) * W + (tap % 3 - 1))]; }
+};
+
 template <int WN, int WGN>
 __global__ void __launch_bounds__(256)
 conv3x3_kernel(int M, int C_in, int C_out, int W, int H, const float* __restrict__ x, const float* __restrict__ w,
                const float* __restrict__ bias, int relu, float* __restrict__ out)
 {
-    constexpr int WGM = 4 / WGN, BM = 64 * WGM, BN = 32 * WN * WGN, BMP = BM + 32;
-    constexpr int RPT = KC * BM / 256;                     // X rows a thread stages per chunk (36 or 18: whole input channels)
-    __shared__ float Xs[KC * BMP];
-    __shared__ float Ws[BN * KP];
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int m0 = (int)blockIdx.x * BM, n0 = (int)blockIdx.y * BN;
-    const int HW = H * W, K = 9 * C_in;
-
-    // the pixel this thread stages: its offset in a channel plane and which of its 9 taps lie inside the image
-    const int lm = t % BM, lk0 = t / BM;
-    const int p = m0 + lm;
-    size_t base = 0;
-    unsigned inside = 0;
-    if (p < M) {
-        const int img = p / HW, rem = p - img * HW, y = rem / W, xx = rem - y * W;
-        base = (size_t)img * (size_t)C_in * (size_t)HW + (size_t)rem;
-        for (int ky = 0; ky < 3; ky++)
-            for (int kx = 0; kx < 3; kx++)
-                if (y + ky - 1 >= 0 && y + ky - 1 < H && xx + kx - 1 >= 0 && xx + kx - 1 < W) inside |= 1u << (ky * 3 + kx);
-    }
-
-    const int wm_base = (wave % WGM) * 64, wn_base = (wave / WGM) * 32 * WN;
-    f32x16 acc[2][WN];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
-
-    for (int c0 = 0; c0 < C_in; c0 += 4) {
-        const int nci = (C_in - c0 < 4) ? C_in - c0 : 4;
-        const int klen = 9 * nci, kpad = (klen + 1) & ~1;
-        // pixel operand: rows kk = lk0 * RPT + j, all KC of them (rows behind klen are zeros: the pad term, and never NaN)
-#pragma unroll
-        for (int j = 0; j < RPT; j++) {
-            const int kk = lk0 * RPT + j;
-            const int ci = lk0 * (RPT / 9) + j / 9, tap = j % 9;
-            float v = 0.0f;
-            if (kk < klen && ((inside >> tap) & 1u))
-                v = x[base + (size_t)(c0 + ci) * (size_t)HW + (size_t)((tap / 3 - 1) * W + (tap % 3 - 1))];
-            Xs[kk * BMP + lm] = v;
-        }
-        // weight operand: row n = 36 consecutive floats of the weight tensor
-        for (int e = t; e < BN * KC; e += 256) {
-            const int n = e / KC, kk = e - n * KC;
-            Ws[n * KP + kk] = (kk < klen) ? w[(size_t)(n0 + n) * (size_t)K + (size_t)(c0 * 9 + kk)] : 0.0f;
-        }
-        __syncthreads();
-        for (int ks = 0; ks < kpad; ks += 2) {
-            const int kk = ks + (lane >> 5);
-            float a[WN], b[2];
-#pragma unroll
-            for (int j = 0; j < WN; j++) a[j] = Ws[(wn_base + 32 * j + (lane & 31)) * KP + kk];
-#pragma unroll
-            for (int i = 0; i < 2; i++) b[i] = Xs[kk * BMP + wm_base + 32 * i + (lane & 31)];
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int j = 0; j < WN; j++) acc[i][j] = mma_32x32x2(a[j], b[i], acc[i][j]);
-        }
-        __syncthreads();
-    }
-
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const int q = m0 + wm_base + 32 * i + (lane & 31);
-        if (q >= M) continue;
-        const int img = q / HW, rem = q - img * HW;
-        float* o = out + (size_t)img * (size_t)C_out * (size_t)HW + (size_t)rem;
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int co = n0 + wn_base + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                float v = acc[i][j][r] + bias[co];
-                if (relu) v = (v < 0.0f) ? 0.0f : v;
-                o[(size_t)co * (size_t)HW] = v;
-            }
-    }
+    const int HW = H * W;
+    conv3x3::main_loop<WN, WGN, true>(C_in, C_out, BatchOperand{ x, M, C_in, W, H, HW, 0, 0, 0 }, w,
+        [=](const f32x16 (&acc)[2][WN], int m0, int n0, int wm_base, int wn_base, int lane, float*) {
+            conv3x3::for_each_output<WN>(acc, M, m0, n0, wm_base, wn_base, lane, [=](int q) {
+                const int img = q / HW, rem = q - img * HW;
+                float* o = out + (size_t)img * (size_t)C_out * (size_t)HW + (size_t)rem;
+                return [=](int co, float v) {
+                    v = v + bias[co];
+                    if (relu) v = (v < 0.0f) ? 0.0f : v;
+                    o[(size_t)co * (size_t)HW] = v;
+                };
+            });
+        });
 }
 
 // =====================================================================================================================================
@@ -233,16 +172,11 @@ static int launch_conv(int32_t n_img, int32_t c_in, int32_t c_out, int32_t W, in
 {
     const int M = n_img * H * W;
     const int relu_i = relu != 0;
-    if (c_out % 128 == 0) {
-        const dim3 grid((unsigned)((M + 127) / 128), (unsigned)(c_out / 128));
-        hipLaunchKernelGGL((conv3x3_kernel<2, 2>), grid, dim3(256), 0, stream, M, (int)c_in, (int)c_out, (int)W, (int)H, x, w, bias, relu_i, out);
-    } else if (c_out % 64 == 0) {
-        const dim3 grid((unsigned)((M + 255) / 256), (unsigned)(c_out / 64));
-        hipLaunchKernelGGL((conv3x3_kernel<2, 1>), grid, dim3(256), 0, stream, M, (int)c_in, (int)c_out, (int)W, (int)H, x, w, bias, relu_i, out);
-    } else {
-        const dim3 grid((unsigned)((M + 255) / 256), (unsigned)(c_out / 32));
-        hipLaunchKernelGGL((conv3x3_kernel<1, 1>), grid, dim3(256), 0, stream, M, (int)c_in, (int)c_out, (int)W, (int)H, x, w, bias, relu_i, out);
-    }
+#define GOF_LAUNCH_CONV(WN, WGN) hipLaunchKernelGGL((conv3x3_kernel<WN, WGN>), (conv3x3::grid<WN, WGN>(M, c_out)), dim3(256), 0, stream, M, (int)c_in, (int)c_out, (int)W, (int)H, x, w, bias, relu_i, out)
+    if (c_out % 128 == 0) GOF_LAUNCH_CONV(2, 2);
+    else if (c_out % 64 == 0) GOF_LAUNCH_CONV(2, 1);
+    else GOF_LAUNCH_CONV(1, 1);
+#undef GOF_LAUNCH_CONV
     GOF_LAUNCH_CHECK(stream, 0);
     return GOF_OK;
 }

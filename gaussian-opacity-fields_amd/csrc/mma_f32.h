@@ -1,5 +1,5 @@
-// mma_f32.h -- the exact fp32 matrix step of gfx950 (v_mfma_f32_32x32x2_f32) and its host restatement, shared by the units that
-// build their GEMMs on it (lpips.hip, appearance.hip).
+// mma_f32.h -- the exact fp32 matrix step of gfx950 (v_mfma_f32_32x32x2_f32) and its host restatement, shared by the GEMMs that
+// are built on it (conv3x3_f32.h: the convolution of lpips.hip and appearance.hip; appearance.hip's weight gradient).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import appearance_restatement as R
+import conv3x3_pins as P
 
 pytestmark = pytest.mark.gpu
 
@@ -216,6 +217,20 @@ def test_the_reference_signature_with_a_stand_in_model(M, reference):
     want = R.resized(ref64["transformed"], size, torch.float64)
     assert tuple(out.shape) == (3,) + size and not out.requires_grad
     assert torch.allclose(out.cpu().double(), want, rtol=0, atol=2e-5)
+
+
+def test_the_convolution_and_the_narrow_network_give_the_pinned_bits(M):
+    """the SHA-256 of every output of tests/conv3x3_pins.py's appearance cases and of the loss and the 16 gradients of the narrowest
+    network at 32 x 32 (conv3's head epilogue) is the one recorded in tests/golden/conv3x3_pins.json"""
+    got = P.digests("appearance", DEV, app_module=M)
+    assert len(got) == len(P.app_cases()) + 17 and P.unpinned("appearance", "gpu", got) == []
+
+
+def test_the_lpips_and_the_appearance_convolution_give_the_same_bits(M):
+    """gof_lpips_conv3x3 on one image and gof_app_conv3x3 (PLAIN view, no mask, with the bias) are torch.equal for C_out 32, 64, 96 and
+    128 (96 runs different tiles in the two units) at C_in 3, 6 and 8 on the 17 x 9 plane"""
+    import image_metrics
+    assert P.contract_mismatches(DEV, image_metrics, M) == []
 
 
 def test_refusals_on_the_device(M):

@@ -30,6 +30,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "hipemu"))
 import host_child  # noqa: E402
+import conv3x3_pins as P  # noqa: E402
 import appearance_restatement as R  # noqa: E402
 
 SIZES = [(32, 32), (75, 100), (64, 45)]             # (H, W)
@@ -366,6 +367,20 @@ def test_size_queries_and_argument_checks():
     assert b"overlaps" in L.gof_last_error()
     assert C.sizeof(M.GofAppNet) == 28 and M.WGRAD_CHUNK == 4096 and 300 <= -(-1056 * 1600 // M.WGRAD_CHUNK) <= 500
     assert tuple(M.PARAM_NAMES) == tuple(R.PARAM_NAMES)
+
+
+def test_the_convolution_and_the_narrow_network_give_the_pinned_bits(tmp_path):
+    """the SHA-256 of every output of tests/conv3x3_pins.py's appearance cases (every view, tile shape, zero-row pattern, with and without
+    mask / bias / ReLU) and of the loss and the 16 gradients of the narrowest network at 32 x 32 (conv3's head epilogue) is the one
+    recorded in tests/golden/conv3x3_pins.json: the order of K has not moved"""
+    got = P.emulated("appearance", tmp_path)
+    assert len(got) == len(P.app_cases()) + 17 and P.unpinned("appearance", "host", got) == []
+
+
+def test_the_lpips_and_the_appearance_convolution_give_the_same_bits(tmp_path):
+    """one main loop, one order of K: gof_lpips_conv3x3 on one image and gof_app_conv3x3 (PLAIN view, no mask, with the bias) are
+    torch.equal for C_out 32, 64, 96 and 128 (96 runs different tiles in the two units) at C_in 3, 6 and 8 on the 17 x 9 plane"""
+    assert P.emulated("contract", tmp_path) == []
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import lpips_restatement as R
+import conv3x3_pins as P
 
 pytestmark = pytest.mark.gpu
 
@@ -183,6 +184,12 @@ def test_the_lines_of_metrics_py_restated(net, reference, stand_ins, tmp_path, m
     assert str(tmp_path / "absent.pth") in str(e.value) and str(tmp_path / "torch_home" / "hub" / "checkpoints" / "vgg.pth") in str(e.value)
     with pytest.raises(NotImplementedError):
         lpips.LPIPS(net='alex')
+
+
+def test_the_convolution_gives_the_pinned_bits(net):
+    """the SHA-256 of every output of tests/conv3x3_pins.py's LPIPS cases is the one recorded in tests/golden/conv3x3_pins.json"""
+    got = P.digests("lpips", DEV, lpips_module=net[0])
+    assert len(got) == len(P.lpips_cases()) and P.unpinned("lpips", "gpu", got) == []
 
 
 def test_refusals_on_the_device(net):

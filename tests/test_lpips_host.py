@@ -18,6 +18,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "hipemu"))
 import host_child  # noqa: E402
+import conv3x3_pins as P  # noqa: E402
 import lpips_restatement as R  # noqa: E402
 
 SIZES = [(16, 16), (37, 53), (24, 20)]
@@ -213,6 +214,13 @@ def test_size_queries_and_argument_checks():
     assert L.gof_lpips_maxpool2(1, 1, 8, None, None, None) < 0
     assert C.sizeof(M.GofLpipsLayer) == 16
     assert M.VGG_LAYERS == R.vgg_layers() and M.SHIFT == R.SHIFT and M.SCALE == R.SCALE
+
+
+def test_the_convolution_gives_the_pinned_bits(tmp_path):
+    """the SHA-256 of every output of tests/conv3x3_pins.py's LPIPS cases (two images of 17 x 9, C_in 3 / 6 / 8, every tile shape, with and
+    without the ReLU) is the one recorded in tests/golden/conv3x3_pins.json: the order of K has not moved"""
+    got = P.emulated("lpips", tmp_path)
+    assert len(got) == len(P.lpips_cases()) and P.unpinned("lpips", "host", got) == []
 
 
 if __name__ == "__main__":
