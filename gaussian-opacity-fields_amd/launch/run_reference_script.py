@@ -89,6 +89,14 @@ What it does, in this order (nothing in the reference checkout is edited):
      objects) goes to the function that was bound before.  image_writer.flush() runs after the script's __main__ returns or raises (and at
      exit): an error of the writer thread surfaces there.  Its speed has not been measured on the device yet, so the binding is asked for
      (PNG_WRITER_BY_DEFAULT below); GOF_PIL_PNG=1 leaves the function alone whatever else is set.
+ 16. metrics.py:25-36 defines readImages: for every test view it opens two PNG files with Pillow (inflate and unfilter on one CPU thread),
+     divides by 255 through to_tensor and uploads from pageable memory, for all views of a method before the first metric.  With
+     GOF_HIP_PNG_READ=1 the script's name becomes png_reader.read_images_for_metrics (csrc/png_decode.hip: inflate, the PNG filters and the
+     conversion to float planes on the device for a batch of files; worker threads read the files and walk the chunks), rebound as 6.
+     rebinds `evaluage_alpha`: the same file order, the same three lists, the tensors bit-identical.  A file the unit does not take
+     (interlaced, not 8 bits, a palette, tRNS) goes through the script's own function, which run_script keeps (SCRIPT_OWN).  Its speed has
+     not been measured on the device yet, so the binding is asked for (PNG_READER_BY_DEFAULT below); GOF_PIL_PNG_READ=1 leaves the script
+     alone whatever else is set.  scene_images' decoding of PNG training images stays Pillow's.
 """
 import importlib
 import os
@@ -479,6 +487,32 @@ def rebind_png_writer():
     tvu.save_image = _save_image
 
 
+# Whether metrics.py's readImages is rebound without being asked for: decided by the measured time of reading one scene's files
+# (profiles/png_decode.md).  Until that record shows the device path faster than the script's own loop AND than a Pillow thread pool,
+# GOF_HIP_PNG_READ=1 asks for it.
+PNG_READER_BY_DEFAULT = False
+
+# the functions a script defined itself under the names run_script replaced: {name: the script's own function}
+SCRIPT_OWN = {}
+
+
+def _read_images_for_metrics(renders_dir, gt_dir):
+    import png_reader
+    png_reader.previous = SCRIPT_OWN.get("readImages")
+    return png_reader.read_images_for_metrics(renders_dir, gt_dir)
+
+
+def png_reader_rebinding(script):
+    """the names to replace in `script`'s namespace for the PNG decoder (metrics.py:25-36): `readImages` for every script that defines
+    it.  GOF_PIL_PNG_READ=1 keeps the script's own function whatever else is set; while the binding is not the default,
+    GOF_HIP_PNG_READ=1 asks for it.  The replacement imports png_reader when it is called, not here."""
+    if os.environ.get("GOF_PIL_PNG_READ", "0") == "1":
+        return {}
+    if not PNG_READER_BY_DEFAULT and os.environ.get("GOF_HIP_PNG_READ", "0") != "1":
+        return {}
+    return {"readImages": _read_images_for_metrics}
+
+
 def flush_png_writer():
     """wait for the files image_writer still holds; re-raises the first error of its writer thread"""
     iw = sys.modules.get("image_writer")
@@ -612,6 +646,7 @@ def main():
     rebind.update(dtu_eval_rebinding(script))
     rebind.update(dtu_cull_rebinding(script))
     rebind.update(appearance_rebinding(script))
+    rebind.update(png_reader_rebinding(script))
     try:
         run_script(script, rebind)
     except BaseException:
@@ -663,6 +698,7 @@ def run_script(script, rebind):
         head = ast.Module(body=[n for n in tree.body if not _is_main_guard(n)], type_ignores=[])
         exec(compile(head, script, "exec"), mod.__dict__)
         for k in names:
+            SCRIPT_OWN[k] = mod.__dict__.get(k)
             mod.__dict__[k] = rebind[k]
         exec(compile(ast.Module(body=guards, type_ignores=[]), script, "exec"), mod.__dict__)
     finally:
