@@ -29,9 +29,11 @@
 #include "../../include/gof_hip.h"
 #include "../../include/gof_png_read_hip.h"
 #include "gof_common.h"
+#include "png_common.h"
 
 namespace gof {
 namespace pngr {
+using namespace pngc;
 
 constexpr int THREADS = 256;
 constexpr int WIN = 4096;                       // bytes of the stream staged per round
@@ -39,10 +41,8 @@ constexpr int WIN_WORDS = WIN / 4;
 constexpr int WIN_PAD = 4;                      // zero words behind the window: a token that starts inside the limit ends inside them
 constexpr uint32_t WIN_LIMIT_BITS = (WIN - 16) * 8;     // no token starts behind this bit of the window
 constexpr int BATCH = 512;                      // tokens per round: at most 48 bits each, 3072 bytes < WIN - 16
-constexpr int LBITS = 10, DBITS = 9, CBITS = 7; // first-level table sizes: literal / length, distance, code lengths
-constexpr int NLIT = 288, NDIST = 32, NCL = 19, MAXBITS = 15;
-constexpr uint32_t ADLER = 65521u;
-constexpr int ADLER_BLOCK = 16384;              // bytes per partial-sum step: 64 per thread, (n - i) * byte sums stay below 2^32
+constexpr int LBITS = 10, DBITS = 9;            // first-level table sizes: literal / length, distance (the code lengths': CL_MAXBITS, every code)
+constexpr int NLIT_READ = 288, NDIST = 32;      // code lengths read: the fixed code gives 288 and 32 (a block may use 286 and 30 of them)
 constexpr uint32_t LITERAL = 0x80000000u;
 static_assert(BATCH * 6 + 600 < WIN - 16, "a round's tokens and a dynamic header fit the window");
 
@@ -84,7 +84,7 @@ struct Bits {
 
 struct Code {
     uint32_t count[MAXBITS + 1];                // symbols per code length
-    uint16_t sorted[NLIT];                      // the symbols by (length, symbol)
+    uint16_t sorted[NLIT_READ];                      // the symbols by (length, symbol)
 };
 
 // one symbol: the first-level table, or (an entry of length 0: a longer code, or no code) the canonical walk, one bit per length
@@ -123,14 +123,14 @@ __device__ bool build_tables(const uint8_t* lens, int n, uint16_t* table, int tb
     int left = 1;
     uint32_t total = 0u;
     bool over = false;
-    offs[1] = 0u; next[1] = 0u;
+    first_codes<MAXBITS>(code.count, next);
+    offs[1] = 0u;
     for (int l = 1; l <= MAXBITS; l++) {
         const uint32_t cnt = code.count[l];
         left = 2 * left - (int)cnt;
         if (left < 0) { over = true; left = 0; }
         total += cnt;
         offs[l + 1] = offs[l] + cnt;
-        next[l + 1] = (next[l] + cnt) << 1;
     }
     const bool ok = !over && (left == 0 || (total == 0u && may_be_empty) || (total == 1u && code.count[1] == 1u));
     if (ok) {
@@ -141,7 +141,7 @@ __device__ bool build_tables(const uint8_t* lens, int n, uint16_t* table, int tb
             for (int q = 0; q < s; q++) rank += lens[q] == l ? 1u : 0u;
             code.sorted[offs[l] + rank] = (uint16_t)s;
             if (l <= tbits) {
-                const uint32_t r = __brev(next[l] + rank) >> (32 - l);
+                const uint32_t r = reversed_code(next, l, rank);
                 for (uint32_t i = r; i < (1u << tbits); i += 1u << l) table[i] = (uint16_t)((s << 4) | l);
             }
         }
@@ -156,8 +156,8 @@ struct InflateLds {
     uint32_t tok_info[BATCH];                   // LITERAL | byte, or length | distance << 9
     uint16_t lit_table[1 << LBITS];
     uint16_t dist_table[1 << DBITS];
-    uint16_t cl_table[1 << CBITS];
-    uint8_t lens[NLIT + NDIST + 4];             // the literal / length code lengths, the distance code lengths behind them
+    uint16_t cl_table[1 << CL_MAXBITS];
+    uint8_t lens[NLIT_READ + NDIST + 4];             // the literal / length code lengths, the distance code lengths behind them
     Code lit, dist;
     uint32_t adler[2];
     // the state thread 0 carries from round to round, and the round's parallel job
@@ -192,38 +192,37 @@ __device__ void parse_header(InflateLds& L, Bits& b, uint64_t base, uint32_t val
         return;
     }
     if (type == 1u) {
-        for (int i = 0; i < NLIT; i++) L.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
-        for (int i = 0; i < NDIST; i++) L.lens[NLIT + i] = 5;
-        L.nl = NLIT; L.nd = NDIST;
+        for (int i = 0; i < NLIT_READ; i++) L.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
+        for (int i = 0; i < NDIST; i++) L.lens[NLIT_READ + i] = 5;
+        L.nl = NLIT_READ; L.nd = NDIST;
     } else {
         const uint32_t hlit = b.get(5) + 257u, hdist = b.get(5) + 1u, hclen = b.get(4) + 4u;
         if (hlit > 286u || hdist > 30u) return fail(L, GOF_PNG_READ_E_CODE_LENGTHS);
-        const uint8_t order[NCL] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
         uint8_t cl[NCL];
-        uint32_t count[CBITS + 1], next[CBITS + 2];
+        uint32_t count[CL_MAXBITS + 1], next[CL_MAXBITS + 2];
         for (int i = 0; i < NCL; i++) cl[i] = 0;
-        for (int i = 0; i <= CBITS; i++) count[i] = 0u;
-        for (uint32_t i = 0; i < hclen; i++) { const uint32_t l = b.get(3); cl[order[i]] = (uint8_t)l; }
+        for (int i = 0; i <= CL_MAXBITS; i++) count[i] = 0u;
+        for (uint32_t i = 0; i < hclen; i++) { const uint32_t l = b.get(3); cl[cl_order((int)i)] = (uint8_t)l; }
         for (int i = 0; i < NCL; i++) count[cl[i]]++;
+        first_codes<CL_MAXBITS>(count, next);
         int left = 1;
-        next[1] = 0u;
-        for (int l = 1; l <= CBITS; l++) {
+        for (int l = 1; l <= CL_MAXBITS; l++) {
             left = 2 * left - (int)count[l];
             if (left < 0) return fail(L, GOF_PNG_READ_E_CODE_LENGTHS);
-            next[l + 1] = (next[l] + count[l]) << 1;
         }
         if (left != 0) return fail(L, GOF_PNG_READ_E_CODE_LENGTHS);         // (the code-length code must be complete)
-        for (int s = 0; s < NCL; s++) {
+        for (int s = 0; s < NCL; s++) {                                     // (in symbol order: next[l] becomes the next symbol's first code)
             const int l = cl[s];
             if (!l) continue;
-            const uint32_t r = __brev(next[l]++) >> (32 - l);
-            for (uint32_t i = r; i < (1u << CBITS); i += 1u << l) L.cl_table[i] = (uint16_t)((s << 4) | l);
+            const uint32_t r = reversed_code(next, l, 0u);
+            next[l]++;
+            for (uint32_t i = r; i < (1u << CL_MAXBITS); i += 1u << l) L.cl_table[i] = (uint16_t)((s << 4) | l);
         }
         const uint32_t total = hlit + hdist;    // one run of lengths: a repeat may cross from the literal / length set into the distances
         uint32_t i = 0;
         while (i < total) {
             b.refill();
-            const uint32_t e = L.cl_table[b.peek(CBITS)];
+            const uint32_t e = L.cl_table[b.peek(CL_MAXBITS)];
             b.skip((int)(e & 15u));
             const uint32_t sym = e >> 4;
             if (b.used() > valid_bits) return fail(L, GOF_PNG_READ_E_TRUNCATED);
@@ -241,9 +240,9 @@ __device__ void parse_header(InflateLds& L, Bits& b, uint64_t base, uint32_t val
         if (b.used() > valid_bits) return fail(L, GOF_PNG_READ_E_TRUNCATED);
         if (L.lens[256] == 0) return fail(L, GOF_PNG_READ_E_CODE_LENGTHS);
         // the distance lengths to their own place
-        if (hlit < (uint32_t)NLIT) {
-            for (int k = (int)hdist - 1; k >= 0; k--) L.lens[NLIT + k] = L.lens[hlit + k];
-            for (uint32_t k = hlit; k < (uint32_t)NLIT; k++) L.lens[k] = 0;
+        if (hlit < (uint32_t)NLIT_READ) {
+            for (int k = (int)hdist - 1; k >= 0; k--) L.lens[NLIT_READ + k] = L.lens[hlit + k];
+            for (uint32_t k = hlit; k < (uint32_t)NLIT_READ; k++) L.lens[k] = 0;
         }
         L.nl = hlit; L.nd = hdist;
     }
@@ -350,7 +349,7 @@ inflate(const DevImage* __restrict__ images, int32_t* __restrict__ status)
             if (tid == 0) L.out_pos += len;
         } else if (job == JOB_BUILD) {
             const bool a = build_tables(L.lens, (int)L.nl, L.lit_table, LBITS, L.lit, false);
-            const bool d = build_tables(L.lens + NLIT, (int)L.nd, L.dist_table, DBITS, L.dist, true);
+            const bool d = build_tables(L.lens + NLIT_READ, (int)L.nd, L.dist_table, DBITS, L.dist, true);
             if (tid == 0 && !(a && d)) fail(L, GOF_PNG_READ_E_CODE_LENGTHS);
         } else if (job == JOB_WRITE) {
             const uint32_t start = L.out_pos, total = L.job_len, ntok = L.ntok;
@@ -375,24 +374,21 @@ inflate(const DevImage* __restrict__ images, int32_t* __restrict__ status)
     }
     __syncthreads();
     if (L.phase == PH_DONE) {
-        // the trailer behind the last block's padding; Adler-32 of the output in steps of ADLER_BLOCK
+        // the trailer behind the last block's padding; Adler-32 of the output in steps of ADLER_STEP
         const uint64_t trailer = (L.bitpos + 7u) >> 3;
         const bool complete = L.out_pos == cap && trailer + 4u <= n;
         uint32_t s1 = 1u, s2 = 0u;              // (thread 0's)
         if (complete) {
-            for (uint32_t b0 = 0; b0 < cap; b0 += (uint32_t)ADLER_BLOCK) {
-                const uint32_t nb = cap - b0 < (uint32_t)ADLER_BLOCK ? cap - b0 : (uint32_t)ADLER_BLOCK;
+            for (uint32_t b0 = 0; b0 < cap; b0 += (uint32_t)ADLER_STEP) {
+                const uint32_t nb = cap - b0 < (uint32_t)ADLER_STEP ? cap - b0 : (uint32_t)ADLER_STEP;
                 if (tid == 0) { L.adler[0] = 0u; L.adler[1] = 0u; }
                 __syncthreads();
                 uint32_t a = 0u, w = 0u;
-                for (uint32_t i = tid; i < nb; i += THREADS) { const uint32_t v = out[b0 + i]; a += v; w += (nb - i) * v; }
+                adler_partial(nb, (uint32_t)tid, nb, (uint32_t)THREADS, [&](uint32_t i) { return (uint32_t)out[b0 + i]; }, a, w);
                 atomicAdd(&L.adler[0], a % ADLER);
                 atomicAdd(&L.adler[1], w % ADLER);
                 __syncthreads();
-                if (tid == 0) {
-                    s2 = (uint32_t)(((uint64_t)s2 + (uint64_t)nb * s1 + L.adler[1]) % ADLER);
-                    s1 = (s1 + L.adler[0]) % ADLER;
-                }
+                if (tid == 0) adler_append(s1, s2, nb, L.adler[0], L.adler[1]);
             }
         }
         if (tid == 0) {
@@ -426,10 +422,8 @@ __device__ __forceinline__ uint32_t reconstruct(uint32_t ft, uint32_t raw, uint3
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int a = (int)((left >> (8 * k)) & 255u), b = (int)((up >> (8 * k)) & 255u), c = (int)((upleft >> (8 * k)) & 255u);
-        const int p = a + b - c;
-        const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-        const int paeth = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-        const int pred = ft == 0u ? 0 : ft == 1u ? a : ft == 2u ? b : ft == 3u ? (a + b) >> 1 : paeth;
+        const int pth = paeth(a, b, c);         // (formed for every filter: selects, no branch per byte)
+        const int pred = ft == 0u ? 0 : ft == 1u ? a : ft == 2u ? b : ft == 3u ? (a + b) >> 1 : pth;
         r |= ((((raw >> (8 * k)) & 255u) + (uint32_t)pred) & 255u) << (8 * k);
     }
     return r;

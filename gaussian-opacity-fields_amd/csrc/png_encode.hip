@@ -28,22 +28,21 @@
 #include "../../include/gof_png_hip.h"
 #include "gof_common.h"
 #include "radix.h"
+#include "png_common.h"
 
 namespace gof {
 namespace png {
+using namespace pngc;
 
 constexpr int THREADS = 256;
 constexpr int BLOCK = GOF_PNG_BLOCK_BYTES;
 constexpr int SEG = BLOCK / THREADS;            // bytes of a block one thread owns
 constexpr int SLOT = BLOCK + 16;                // bytes of a block's slot in the workspace (a stored block: BLOCK + 5), a multiple of 16
 constexpr int OUT_WORDS = SLOT / 4;
-constexpr int NLIT = 286;                       // literal / length symbols
-constexpr int NCL = 19;                         // code-length symbols
-constexpr int MAXBITS = 15;
-constexpr int CL_MAXBITS = 7;
+constexpr int NLIT_WRITTEN = 286;               // literal / length symbols a block may use (the decoder reads 288 lengths: the fixed code's)
 constexpr int CH = 1024;                        // pixels of a row quantise_filter stages at a time
-constexpr uint32_t ADLER = 65521u;
 static_assert(BLOCK % THREADS == 0 && SEG == 64 && SLOT % 16 == 0, "deflate_blocks: one thread owns 64 bytes");
+static_assert(BLOCK <= ADLER_STEP, "deflate_blocks: a block is one Adler-32 step");
 
 // (uint8)clamp(x * 255 + 0.5, 0, 255) with the product and the sum rounded separately; NaN fails the first comparison: 0
 __device__ __forceinline__ uint32_t quantise(float x)
@@ -91,11 +90,8 @@ quantise_filter(const float* __restrict__ planes, int64_t pstride, int C, int W,
             __syncthreads();
             for (int j = tid; j < 3 * npix; j += THREADS) {
                 const int cur = s_cur[3 + j], a = s_cur[j], b = s_up[3 + j], c = s_up[j];
-                const int p = a + b - c;
-                const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-                const int paeth = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
                 const uint32_t f[5] = { (uint32_t)cur, (uint32_t)(cur - a) & 255u, (uint32_t)(cur - b) & 255u, (uint32_t)(cur - ((a + b) >> 1)) & 255u,
-                                        (uint32_t)(cur - paeth) & 255u };
+                                        (uint32_t)(cur - paeth(a, b, c)) & 255u };
                 if (pass == 0) {
 #pragma unroll
                     for (int k = 0; k < 5; k++) sum[k] += abs_signed(f[k]);
@@ -154,10 +150,10 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, Op op, uint32_t ident
 
 // ---- optimal length-limited prefix code (package-merge), by the whole workgroup ---------------------------------------------------
 struct TreeScratch {
-    uint32_t w[NLIT];                           // the used symbols' frequencies, ascending by (frequency, symbol)
-    uint16_t sym[NLIT];
-    uint32_t list[2][2 * NLIT + 4];             // the merged list of a level and of the level below it
-    uint16_t pos[MAXBITS][NLIT];                // where leaf i stands in the merged list of a level
+    uint32_t w[NLIT_WRITTEN];                           // the used symbols' frequencies, ascending by (frequency, symbol)
+    uint16_t sym[NLIT_WRITTEN];
+    uint32_t list[2][2 * NLIT_WRITTEN + 4];             // the merged list of a level and of the level below it
+    uint16_t pos[MAXBITS][NLIT_WRITTEN];                // where leaf i stands in the merged list of a level
     uint32_t n;
     uint32_t count[MAXBITS + 1];                // symbols per code length
 };
@@ -234,16 +230,15 @@ __device__ void build_code(const uint32_t* freq, int nsym, int L, uint8_t* len, 
     }
     __syncthreads();
     // canonical codes: by length, then by symbol
-    uint32_t next[MAXBITS + 2];
-    next[0] = 0u; next[1] = 0u;
-    for (int l = 2; l <= MAXBITS; l++) next[l] = (next[l - 1] + S.count[l - 1]) << 1;
+    uint32_t first[MAXBITS + 2];
+    first_codes<MAXBITS>(S.count, first);
     for (int a = tid; a < nsym; a += THREADS) {
         const int l = len[a];
         uint32_t v = 0u;
         if (l) {
             uint32_t before = 0u;
             for (int b = 0; b < a; b++) before += (len[b] == l) ? 1u : 0u;
-            v = __brev(next[l] + before) >> (32 - l);
+            v = reversed_code(first, l, before);
         }
         code[a] = (uint16_t)v;
     }
@@ -311,9 +306,9 @@ __device__ __forceinline__ void walk_tokens(const uint8_t* s_in, int a, int b, i
 struct DeflateLds {
     uint8_t in[BLOCK + 4 * THREADS];
     uint32_t out[OUT_WORDS];
-    uint32_t hist[NLIT + 2];
-    uint8_t len[NLIT + 2];
-    uint16_t code[NLIT + 2];
+    uint32_t hist[NLIT_WRITTEN + 2];
+    uint8_t len[NLIT_WRITTEN + 2];
+    uint16_t code[NLIT_WRITTEN + 2];
     uint32_t cl_hist[NCL + 1];
     uint8_t cl_len[NCL + 1];
     uint16_t cl_code[NCL + 1];
@@ -323,7 +318,7 @@ struct DeflateLds {
     uint32_t hlit, hdr_bits;
 };
 
-// raw: the scanline stream of `total` bytes; slots: [blocks][SLOT]; sizes: [blocks]; sums: [blocks] {sum of bytes, sum of (n - i) byte_i} mod 65521
+// raw: the scanline stream of `total` bytes; slots: [blocks][SLOT]; sizes: [blocks]; sums: [blocks] {sum of bytes, sum of (n - i) byte_i} mod ADLER
 __global__ void __launch_bounds__(THREADS)
 deflate_blocks(const uint8_t* __restrict__ raw, uint32_t total, uint8_t* __restrict__ slots, uint32_t* __restrict__ sizes, uint2* __restrict__ sums)
 {
@@ -336,7 +331,7 @@ deflate_blocks(const uint8_t* __restrict__ raw, uint32_t total, uint8_t* __restr
     const uint8_t* src = raw + base;
     for (int i = tid; i < n; i += THREADS) L.in[at(i)] = src[i];
     for (int i = tid; i < OUT_WORDS; i += THREADS) L.out[i] = 0u;
-    for (int i = tid; i < NLIT + 2; i += THREADS) L.hist[i] = 0u;
+    for (int i = tid; i < NLIT_WRITTEN + 2; i += THREADS) L.hist[i] = 0u;
     if (tid < NCL + 1) L.cl_hist[tid] = 0u;
     if (tid < 2) L.adler[tid] = 0u;
     __syncthreads();
@@ -344,11 +339,9 @@ deflate_blocks(const uint8_t* __restrict__ raw, uint32_t total, uint8_t* __restr
     // the run starts of this thread's bytes, and Adler-32's two sums
     uint32_t last = 0u, first = (uint32_t)n, s1 = 0u, s2 = 0u;            // last: position + 1, 0 = none
     for (int i = a; i < b; i++) {
-        const uint32_t v = L.in[at(i)];
-        if (i == 0 || L.in[at(i - 1)] != v) { last = (uint32_t)i + 1u; if (first == (uint32_t)n) first = (uint32_t)i; }
-        s1 += v;
-        s2 += (uint32_t)(n - i) * v;                                        // < 64 * 16384 * 255
+        if (i == 0 || L.in[at(i - 1)] != L.in[at(i)]) { last = (uint32_t)i + 1u; if (first == (uint32_t)n) first = (uint32_t)i; }
     }
+    adler_partial((uint32_t)n, (uint32_t)a, (uint32_t)b, 1u, [&](uint32_t i) { return (uint32_t)L.in[at((int)i)]; }, s1, s2);
     atomicAdd(&L.adler[0], s1 % ADLER);
     atomicAdd(&L.adler[1], s2 % ADLER);
     uint32_t unused;
@@ -357,14 +350,14 @@ deflate_blocks(const uint8_t* __restrict__ raw, uint32_t total, uint8_t* __restr
     // 1. histogram
     walk_tokens(L.in, a, b, run_before, run_after,
                 [&](uint32_t v) { atomicAdd(&L.hist[v], 1u); },
-                [&](int m) { int sym, eb; uint32_t ev; length_symbol(m, sym, eb, ev); atomicAdd(&L.hist[sym], 1u); atomicAdd(&L.hist[NLIT], 1u); });
+                [&](int m) { int sym, eb; uint32_t ev; length_symbol(m, sym, eb, ev); atomicAdd(&L.hist[sym], 1u); atomicAdd(&L.hist[NLIT_WRITTEN], 1u); });
     if (tid == 0) L.hist[256] = 1u;
     __syncthreads();
-    const bool any_match = L.hist[NLIT] != 0u;
-    build_code(L.hist, NLIT, MAXBITS, L.len, L.code, L.tree);
+    const bool any_match = L.hist[NLIT_WRITTEN] != 0u;
+    build_code(L.hist, NLIT_WRITTEN, MAXBITS, L.len, L.code, L.tree);
     // the code lengths' own code: HLIT lengths and one distance length (1 bit for distance 1 where a match exists), no repeat symbols
     if (tid == 0) {
-        int h = NLIT;
+        int h = NLIT_WRITTEN;
         while (h > 257 && L.len[h - 1] == 0) h--;
         L.hlit = (uint32_t)h;
     }
@@ -376,9 +369,8 @@ deflate_blocks(const uint8_t* __restrict__ raw, uint32_t total, uint8_t* __restr
     build_code(L.cl_hist, NCL, CL_MAXBITS, L.cl_len, L.cl_code, L.tree);
     // 2. thread 0 writes the header; every thread measures its tokens
     if (tid == 0) {
-        const int order[NCL] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
         int hclen = NCL;
-        while (hclen > 4 && L.cl_len[order[hclen - 1]] == 0) hclen--;
+        while (hclen > 4 && L.cl_len[cl_order(hclen - 1)] == 0) hclen--;
         BitWriter w(L.out, 0u);
         w.put(last_block ? 1u : 0u, 1);
         w.put(2u, 2);
@@ -386,7 +378,7 @@ deflate_blocks(const uint8_t* __restrict__ raw, uint32_t total, uint8_t* __restr
         w.put(0u, 5);
         w.put((uint32_t)(hclen - 4), 4);
         uint32_t bits = 17u + 3u * (uint32_t)hclen;
-        for (int i = 0; i < hclen; i++) w.put(L.cl_len[order[i]], 3);
+        for (int i = 0; i < hclen; i++) w.put(L.cl_len[cl_order(i)], 3);
         for (int i = 0; i <= hlit; i++) {
             const int l = i < hlit ? L.len[i] : (any_match ? 1 : 0);
             w.put(L.cl_code[l], L.cl_len[l]);
@@ -449,11 +441,9 @@ compact(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes, c
     for (uint32_t i = threadIdx.x; i < n; i += THREADS) dst[i] = slot[i];
     if (blk == 0 && threadIdx.x == 0) {
         uint32_t s1 = 1u, s2 = 0u;
-        for (uint32_t k = 0; k < gridDim.x; k++) {                          // block order: s2 gains n_k times the s1 in front of the block
-            const uint32_t nk = min((uint32_t)BLOCK, total_in - k * (uint32_t)BLOCK);
+        for (uint32_t k = 0; k < gridDim.x; k++) {                          // in block order
             const uint2 p = sums[k];
-            s2 = (uint32_t)(((uint64_t)s2 + (uint64_t)nk * s1 + p.y) % ADLER);
-            s1 = (s1 + p.x) % ADLER;
+            adler_append(s1, s2, min((uint32_t)BLOCK, total_in - k * (uint32_t)BLOCK), p.x, p.y);
         }
         const size_t body = *total_dev;
         out[0] = 0x78; out[1] = 0x9C;

@@ -22,12 +22,12 @@ import os
 import queue
 import struct
 import threading
-import zlib
 
 import torch
 
 from diff_gaussian_rasterization import _backend as B
 import gof_native as gn
+from png_chunks import SIGNATURE, chunk as _chunk, walk as _walk
 
 __all__ = ["encode_png", "save_image", "flush", "frame", "stream_of", "GofPngEncode", "BLOCK_BYTES", "RING", "IDAT_BYTES", "stats"]
 
@@ -53,7 +53,6 @@ if lib.gof_png_abi_version() != 1:
 BLOCK_BYTES = int(lib.gof_png_block_bytes())    # scanline bytes per deflate block
 RING = 3                                        # pinned buffers: files in flight between the device and the disk
 IDAT_BYTES = 1 << 20                            # bytes of the zlib stream per IDAT chunk
-SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 # the function save_image was bound to before the launcher rebound it (None: torchvision's own, looked up when it is needed)
 previous = None
@@ -118,10 +117,6 @@ def _encode_device(t):
     return out, size, W, H
 
 
-def _chunk(kind, data):
-    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(kind)) & 0xFFFFFFFF)
-
-
 def frame(width, height, stream):
     """the file around a zlib stream: signature, IHDR (8-bit RGB, no interlace), IDAT chunks of IDAT_BYTES, IEND; no ancillary chunks"""
     stream = memoryview(stream)
@@ -134,15 +129,8 @@ def frame(width, height, stream):
 
 
 def stream_of(png):
-    """the zlib stream of a PNG file's IDAT chunks (what frame() was given)"""
-    assert png[:8] == SIGNATURE
-    off, out = 8, []
-    while off < len(png):
-        n, kind = struct.unpack(">I4s", png[off:off + 8])
-        if kind == b"IDAT":
-            out.append(png[off + 8:off + 8 + n])
-        off += 12 + n
-    return b"".join(out)
+    """the zlib stream of a PNG file's IDAT chunks (what frame() was given); ValueError where a chunk's length or CRC-32 is wrong"""
+    return b"".join(bytes(body) for kind, body in _walk(png) if kind == b"IDAT")
 
 
 def _checked(tensor):

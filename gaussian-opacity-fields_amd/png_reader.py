@@ -24,7 +24,6 @@ import collections
 import ctypes as C
 import os
 import struct
-import zlib
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -32,6 +31,7 @@ import torch
 
 from diff_gaussian_rasterization import _backend as B
 import gof_native as gn
+from png_chunks import SIGNATURE, walk as _walk
 
 __all__ = ["read_images", "read_image", "parse", "read_images_for_metrics", "Png", "GofPngImage", "NOT_TAKEN", "STATUS", "GROUP_BYTES", "stats"]
 
@@ -54,7 +54,6 @@ if lib.gof_png_read_abi_version() != 1:
     raise ImportError("png_reader: libgof_hip.so has PNG-read ABI %d, this module is written for 1" % lib.gof_png_read_abi_version())
 
 NOT_TAKEN = None                                # what read_images returns for a file the unit does not take
-SIGNATURE = b"\x89PNG\r\n\x1a\n"
 MAX_DIM = 65535
 MAX_IMAGES = 65535                              # GOF_PNG_READ_MAX_IMAGES
 GROUP_BYTES = 1 << 30                           # device bytes of one group: streams + workspace + outputs
@@ -128,23 +127,12 @@ def parse(src):
 
     def bad(why):
         return ValueError("png_reader: %s: %s" % (name, why))
-    if bytes(data[:8]) != SIGNATURE:
-        raise bad("not a PNG file (signature)")
-    off, ihdr, payloads, trns, ended = 8, None, [], False, False
-    while off < len(data):
-        if off + 12 > len(data):
-            raise bad("a chunk header is cut off at byte %d" % off)
-        n, kind = struct.unpack(">I4s", data[off:off + 8])
-        if off + 12 + n > len(data):
-            raise bad("chunk %r at byte %d claims %d bytes, the file ends before them" % (kind, off, n))
-        body = data[off + 8:off + 8 + n]
-        if struct.unpack(">I", data[off + 8 + n:off + 12 + n])[0] != zlib.crc32(body, zlib.crc32(kind)) & 0xFFFFFFFF:
-            raise bad("chunk %r at byte %d fails its CRC-32" % (kind, off))
-        off += 12 + n
+    ihdr, payloads, trns, ended = None, [], False, False
+    for kind, body in _walk(data, bad):
         if ihdr is None and kind != b"IHDR":
             raise bad("the first chunk is %r, not IHDR" % kind)
         if kind == b"IHDR":
-            if ihdr is not None or n != 13:
+            if ihdr is not None or len(body) != 13:
                 raise bad("a second or malformed IHDR")
             ihdr = struct.unpack(">IIBBBBB", body)
         elif kind == b"IDAT":

@@ -81,3 +81,24 @@ def install_seams(*modules, buffers="workspaces"):
         mod._device_of = lambda t: contextlib.nullcontext()
         mod._device = lambda: torch.device("cpu")
     return check
+
+
+def host_buffers(mod):
+    """-> (alloc, down) of a child process: alloc(nbytes) is one more of the module's own poisoned, guarded buffers, down(t) a numpy copy"""
+    import torch
+    return (lambda nbytes: mod.torch.empty(int(nbytes), dtype=torch.uint8)), (lambda t: t.detach().numpy().copy())
+
+
+def install_transfer_seams(*modules):
+    """install_seams with every buffer guarded, and host stand-ins for the seams of the modules that move data between the host and
+    the device (image_writer, png_reader, scene_images), each where a module has it: the device is "there", an upload, a download and a
+    move to the device are copies, and a pinned buffer is one more poisoned, guarded buffer of the module's.  -> check()"""
+    import torch
+    check = install_seams(*modules, buffers="all")
+    for mod in modules:
+        stand_ins = {"_have_device": lambda: True, "_to_device": lambda t, dev: t.clone(), "_upload": lambda host, dev: host.clone(),
+                     "_download": lambda t: t.clone(), "_pinned": lambda n, mod=mod: mod.torch.empty(int(n), dtype=torch.uint8)}
+        for name, f in stand_ins.items():
+            if hasattr(mod, name):
+                setattr(mod, name, f)
+    return check

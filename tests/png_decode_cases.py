@@ -12,49 +12,11 @@ import numpy as np
 import torch
 
 import png_encode_cases as E
+from png_encode_cases import pillow_file
+from png_restatement import chunk, filter_rows, frame, header, idat_of, paeth  # noqa: F401  (chunk: for the test files)
 
-SIGNATURE = b"\x89PNG\r\n\x1a\n"
-CTYPE = {1: 0, 2: 4, 3: 2, 4: 6}
 # the status words of include/gof_png_read_hip.h
 OK, E_ZLIB_HEADER, E_TRUNCATED, E_BLOCK_TYPE, E_STORED, E_CODE_LENGTHS, E_SYMBOL, E_DISTANCE, E_LONG, E_SHORT, E_ADLER, E_FILTER = range(12)
-
-
-# ---- PNG: framing, filters ---------------------------------------------------------------------------------------------------------------
-def chunk(kind, data):
-    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(kind)) & 0xFFFFFFFF)
-
-
-def frame(w, h, c, stream, idat=None, before=(), after=(), depth=8, ctype=None, interlace=0):
-    """the file around a zlib stream; idat: bytes per IDAT chunk (None: one chunk); before / after: ancillary chunks around the IDATs"""
-    parts = [SIGNATURE, chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, CTYPE[c] if ctype is None else ctype, 0, 0, interlace))]
-    parts += [chunk(k, d) for k, d in before]
-    per = len(stream) if idat is None else idat
-    parts += [chunk(b"IDAT", stream[o:o + per]) for o in range(0, max(1, len(stream)), max(1, per))]
-    parts += [chunk(k, d) for k, d in after]
-    return b"".join(parts + [chunk(b"IEND", b"")])
-
-
-def _paeth(a, b, c):
-    p = a + b - c
-    pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
-    return np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
-
-
-def filter_rows(px, filters):
-    """(H, W, C) uint8, one filter type per row -> the scanline bytes"""
-    H, W, C = px.shape
-    rows = px.reshape(H, W * C).astype(np.int32)
-    out = np.zeros((H, W * C + 1), np.uint8)
-    prev = np.zeros(W * C, np.int32)
-    for y in range(H):
-        cur = rows[y]
-        a = np.concatenate([np.zeros(C, np.int32), cur[:-C]])
-        c = np.concatenate([np.zeros(C, np.int32), prev[:-C]])
-        pred = [0 * cur, a, prev, (a + prev) >> 1, _paeth(a, prev, c)][filters[y]]
-        out[y, 0] = filters[y]
-        out[y, 1:] = (cur - pred) & 255
-        prev = cur
-    return out.tobytes()
 
 
 def unfilter(scan, h, w, c):
@@ -79,9 +41,7 @@ def unfilter(scan, h, w, c):
                 elif ft == 3:
                     p = (a + b) >> 1
                 else:
-                    q = a + b - cc
-                    pa, pb, pc = abs(q - a), abs(q - b), abs(q - cc)
-                    p = a if pa <= pb and pa <= pc else (b if pb <= pc else cc)
+                    p = int(paeth(a, b, cc))
                 cur[i] = (raw[i] + p) & 255
         prev = cur
     return out.astype(np.uint8).reshape(h, w, c)
@@ -96,23 +56,6 @@ def pillow_pixels(png):
     from PIL import Image
     a = np.asarray(Image.open(io.BytesIO(png)))
     return a if a.ndim == 3 else a[:, :, None]
-
-
-def pillow_file(px, **kw):
-    from PIL import Image
-    b = io.BytesIO()
-    Image.fromarray(px if px.shape[2] > 1 else px[:, :, 0]).save(b, format="png", **kw)
-    return b.getvalue()
-
-
-def idat_of(png):
-    off, out = 8, []
-    while off < len(png):
-        n, kind = struct.unpack(">I4s", png[off:off + 8])
-        if kind == b"IDAT":
-            out.append(png[off + 8:off + 8 + n])
-        off += 12 + n
-    return b"".join(out)
 
 
 # ---- a small deflate writer: the streams no library writes ---------------------------------------------------------------------------------
@@ -634,11 +577,6 @@ def needs_encoder(name):
 
 def build(name, IW=None, up=None):
     return CASES[name](IW, up) if needs_encoder(name) else CASES[name]()
-
-
-def header(png):
-    w, h, depth, ctype, _, _, lace = struct.unpack(">IIBBBBB", png[16:29])
-    return w, h, {0: 1, 2: 3, 4: 2, 6: 4}[ctype]
 
 
 def check_file(name, png, planes, pixels):

@@ -1,13 +1,18 @@
 """The cases and the oracles the PNG-encoder test files share (tests/test_png_encode_{host,gpu,launcher}.py): the images,
 torch's CPU arithmetic for the pixels, the scanline stream (filter choice included) restated in numpy, zlib's Z_RLE stream over the same
 bytes, the size allowance, and what each case is there to exercise -- asserted on the restated stream, not assumed."""
+import hashlib
 import heapq
 import io
+import json
+import os
 import struct
 import zlib
 
 import numpy as np
 import torch
+
+from png_restatement import chunks, filter_rows, filtered_rows  # noqa: F401  (chunks: for the test files)
 
 BLOCK = 16384           # GOF_PNG_BLOCK_BYTES: compared with the library's own value by the tests
 
@@ -35,26 +40,8 @@ def quantised(t):
 def scanlines(px):
     """(H, W, 3) uint8 -> the PNG scanline stream: per row the filter (None, Sub, Up, Average, Paeth against the unfiltered previous row,
     zeros above row 0) with the smallest sum of |signed filtered byte|, the lowest number on a tie"""
-    H, W, _ = px.shape
-    rows = px.reshape(H, 3 * W).astype(np.int32)
-    out = np.zeros((H, 3 * W + 1), np.uint8)
-    prev = np.zeros(3 * W, np.int32)
-    for y in range(H):
-        cur = rows[y]
-        a = np.concatenate([np.zeros(3, np.int32), cur[:-3]])
-        b = prev
-        c = np.concatenate([np.zeros(3, np.int32), prev[:-3]])
-        p = a + b - c
-        pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
-        paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
-        cands = [cur, cur - a, cur - b, cur - ((a + b) >> 1), cur - paeth]
-        cands = [(f & 255).astype(np.uint8) for f in cands]
-        sums = [int(np.abs(f.view(np.int8).astype(np.int32)).sum()) for f in cands]
-        k = int(np.argmin(sums))                # (the first minimum)
-        out[y, 0] = k
-        out[y, 1:] = cands[k]
-        prev = cur
-    return out.tobytes()
+    sums = np.abs(filtered_rows(px).view(np.int8).astype(np.int32)).sum(axis=2)
+    return filter_rows(px, sums.argmin(axis=1))     # (the first minimum)
 
 
 def zrle(raw):
@@ -63,25 +50,23 @@ def zrle(raw):
     return c.compress(raw) + c.flush()
 
 
-def pillow_file(px):
+def pillow_file(px, **kw):
+    """(H, W, C) uint8, C in 1..4 -> Pillow's file"""
     from PIL import Image
     b = io.BytesIO()
-    Image.fromarray(px).save(b, format="png")
+    Image.fromarray(px if px.shape[2] > 1 else px[:, :, 0]).save(b, format="png", **kw)
     return b.getvalue()
 
 
-def chunks(png):
-    """[(kind, data)] of a PNG file, every CRC checked"""
-    assert png[:8] == b"\x89PNG\r\n\x1a\n"
-    off, out = 8, []
-    while off < len(png):
-        n, kind = struct.unpack(">I4s", png[off:off + 8])
-        data = png[off + 8:off + 8 + n]
-        assert struct.unpack(">I", png[off + 8 + n:off + 12 + n])[0] == zlib.crc32(kind + data) & 0xFFFFFFFF, kind
-        out.append((kind, data))
-        off += 12 + n
-    assert off == len(png)
-    return out
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "png_encode_pins.json")) as _fh:
+    PINS = json.load(_fh)["cases"]
+
+
+def check_pin(name, png):
+    """the file is byte for byte the pinned one (tests/golden/png_encode_pins.json, written by tests/golden/make_png_encode_pins.py):
+    integer arithmetic and index tie-breaks leave the emulator and the device no room to differ"""
+    pin = PINS[name]
+    assert (len(png), hashlib.sha256(png).hexdigest()) == (pin["bytes"], pin["sha256"]), "%s: %d bytes, not the pinned file of %d bytes" % (name, len(png), pin["bytes"])
 
 
 def has_run3(raw, lo=0, hi=None):
@@ -260,6 +245,7 @@ def check_cases(res, names):
     for n in names:
         png = res["png_" + n].tobytes()
         assert res["again_" + n].tobytes() == png, "%s: two encodes of one input differ" % n
+        check_pin(n, png)
         rows.append(check_png(n, png, tensor(n)))
     return rows
 
@@ -320,6 +306,7 @@ def check_entry(res, block=BLOCK):
     stream_bytes = H * (3 * W + 1)
     assert blk == block and abi == 1 and main_abi == 12
     assert need > 0 and cap == stream_bytes + 5 * (-(-stream_bytes // block)) + 6, "gof_png_max_bytes is the stored bound"
+    check_pin(ENTRY_CASE, res["png_" + ENTRY_CASE].tobytes())
     want = stream_of(res["png_" + ENTRY_CASE].tobytes())
     for fill in FILLS:
         assert int(res["fill%02x_rc" % fill]) == 0

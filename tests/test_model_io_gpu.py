@@ -12,51 +12,22 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import model_io_cases as K  # noqa: E402
 import model_io_runs as R  # noqa: E402
+from gpu_poison import Poisoned  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-PAD = 256
-
-
-def _inside(nbytes, offset):
-    """a uint8 view of nbytes inside an allocation filled with 0xA5, `offset` bytes behind its start -> (view, the whole allocation)"""
-    import torch
-    whole = torch.full((offset + nbytes + PAD,), 0xA5, dtype=torch.uint8, device="cuda")
-    return whole[offset:offset + nbytes], whole
-
-
-_held = []
+_mem = Poisoned()
+down, guards_intact = _mem.down, _mem.guards_intact
 
 
 def up(a):
     import torch
     a = np.ascontiguousarray(a)
-    view, whole = _inside(a.nbytes, PAD + (1 if a.dtype == np.uint8 else 0))          # (file bytes: an odd address)
-    view.copy_(torch.from_numpy(a.reshape(-1).view(np.uint8).copy()))
-    _held.append((whole, view))
-    return view.view(torch.from_numpy(a[:0]).dtype).reshape(a.shape) if a.dtype != np.uint8 else view
+    return _mem.up(torch.from_numpy(a), offset=1 if a.dtype == np.uint8 else 0)          # (file bytes: an odd address)
 
 
 def alloc(shape):
     import torch
-    n = int(np.prod(shape)) * 4
-    view, whole = _inside(n, PAD)
-    _held.append((whole, view))
-    return view.view(torch.float32).reshape(tuple(shape))
-
-
-def down(t):
-    return t.detach().cpu().numpy().copy()
-
-
-def guards_intact():
-    """the poison in front of and behind every tensor handed out is still there"""
-    n = 0
-    for whole, view in _held:
-        off = view.data_ptr() - whole.data_ptr()
-        assert bool((whole[:off] == 0xA5).all()) and bool((whole[off + view.numel():] == 0xA5).all()), "bytes around a %d-byte tensor were overwritten" % view.numel()
-        n += 1
-    _held.clear()
-    return n
+    return _mem.alloc(int(np.prod(shape)) * 4).view(torch.float32).reshape(tuple(shape))
 
 
 @pytest.fixture(scope="module")
@@ -67,7 +38,7 @@ def golden():
 def _run(case, tmp_path):
     import torch
     import model_io as MIO
-    _held.clear()
+    _mem.clear()
     res = R.RUNS[case](MIO, up, alloc, down, str(tmp_path))
     torch.cuda.synchronize()
     assert guards_intact() > 0

@@ -14,49 +14,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import png_decode_cases as K  # noqa: E402
 import png_encode_cases as E  # noqa: E402
+from gpu_poison import Poisoned  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-PAD = 256
-_held = []
-
-
-def _inside(nbytes):
-    import torch
-    whole = torch.full((PAD + nbytes + PAD,), 0xA5, dtype=torch.uint8, device="cuda")
-    view = whole[PAD:PAD + nbytes]
-    _held.append((whole, view))
-    return view
-
-
-def up(t):
-    import torch
-    v = _inside(t.numel() * 4).view(torch.float32).reshape(t.shape)
-    v.copy_(t)
-    return v
+_mem = Poisoned()
+alloc, down, guards_intact = _mem.alloc, _mem.down, _mem.guards_intact
 
 
 def up_bytes(b):
     import torch
-    v = _inside(max(len(b), 1))
+    v = alloc(max(len(b), 1))
     v[:len(b)].copy_(torch.frombuffer(bytearray(b), dtype=torch.uint8))
     return v
-
-
-def alloc(nbytes):
-    return _inside(int(nbytes))
-
-
-def down(t):
-    return t.detach().cpu().numpy().copy()
-
-
-def guards_intact():
-    n = 0
-    for whole, view in _held:
-        assert bool((whole[:PAD] == 0xA5).all()) and bool((whole[PAD + view.numel():] == 0xA5).all()), "bytes around a %d-byte tensor were overwritten" % view.numel()
-        n += 1
-    _held.clear()
-    return n
 
 
 @pytest.mark.parametrize("names", K.GROUPS, ids=lambda g: g[0])
@@ -77,7 +46,7 @@ def test_corrupt_streams_fail_their_own_image_only():
 def test_workspace_contents_and_argument_errors():
     import torch
     import png_reader as R
-    _held.clear()
+    _mem.clear()
     res = K.run_entry(R, up_bytes, alloc, down)
     torch.cuda.synchronize()
     assert guards_intact() > 0

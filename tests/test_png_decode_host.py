@@ -22,18 +22,7 @@ import host_child  # noqa: E402
 import png_decode_cases as K  # noqa: E402
 
 
-def host_seams(*modules):
-    import torch
-    check = host_child.install_seams(*modules, buffers="all")
-    for m in modules:
-        if hasattr(m, "_pinned"):
-            m._pinned = lambda n: torch.full((int(n) + host_child.GUARD,), 0xA5, dtype=torch.uint8)[:int(n)]
-            m._upload = lambda host, dev: host.clone()
-            m._download = lambda t: t.clone()
-        else:
-            m._have_device = lambda: True
-            m._to_device = lambda t, dev: t.clone()
-    return check
+host_seams = host_child.install_transfer_seams
 
 
 def _child(case, out):
@@ -41,17 +30,12 @@ def _child(case, out):
     import image_writer as IW
     import png_reader as R
     check = host_seams(R, IW)
-
-    def alloc(nbytes):
-        return R.torch.empty(int(nbytes), dtype=torch.uint8)
+    alloc, down = host_child.host_buffers(R)
 
     def up_bytes(b):
         t = alloc(max(len(b), 1))
         t[:len(b)] = torch.frombuffer(bytearray(b), dtype=torch.uint8)
         return t
-
-    def down(t):
-        return t.detach().numpy().copy()
     kind, _, names = case.partition(":")
     if kind == "cases":
         res = K.run_cases(R, IW, lambda t: t.clone(), down, names.split(","))

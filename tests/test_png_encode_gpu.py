@@ -12,49 +12,19 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import png_encode_cases as K  # noqa: E402
+from gpu_poison import Poisoned  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-PAD = 256
-_held = []
-
-
-def _inside(nbytes):
-    import torch
-    whole = torch.full((PAD + nbytes + PAD,), 0xA5, dtype=torch.uint8, device="cuda")
-    view = whole[PAD:PAD + nbytes]
-    _held.append((whole, view))
-    return view
-
-
-def up(t):
-    import torch
-    v = _inside(t.numel() * 4).view(torch.float32).reshape(t.shape)
-    v.copy_(t)
-    return v
-
-
-def alloc(nbytes):
-    return _inside(int(nbytes))
-
-
-def down(t):
-    return t.detach().cpu().numpy().copy()
-
-
-def guards_intact():
-    n = 0
-    for whole, view in _held:
-        assert bool((whole[:PAD] == 0xA5).all()) and bool((whole[PAD + view.numel():] == 0xA5).all()), "bytes around a %d-byte tensor were overwritten" % view.numel()
-        n += 1
-    _held.clear()
-    return n
+_mem = Poisoned()
+up, alloc, down, guards_intact = _mem.up, _mem.alloc, _mem.down, _mem.guards_intact
 
 
 @pytest.mark.parametrize("names", K.GROUPS, ids=lambda g: g[0])
 def test_files_decode_to_torchs_bytes_and_streams_to_the_restated_scanlines(names):
+    """every check of the emulated run, the pinned bytes (tests/golden/png_encode_pins.json) included: the device writes the emulator's file"""
     import torch
     import image_writer as IW
-    _held.clear()
+    _mem.clear()
     res = K.run_cases(IW, up, alloc, down, names)
     torch.cuda.synchronize()
     assert guards_intact() > 0
@@ -64,7 +34,7 @@ def test_files_decode_to_torchs_bytes_and_streams_to_the_restated_scanlines(name
 def test_workspace_contents_and_argument_errors():
     import torch
     import image_writer as IW
-    _held.clear()
+    _mem.clear()
     res = K.run_entry(IW, up, alloc, down)
     torch.cuda.synchronize()
     assert guards_intact() > 0
@@ -84,6 +54,7 @@ def test_a_side_stream_gives_the_same_bytes():
     assert guards_intact() > 0
     for n in names:
         assert first["png_" + n].tobytes() == second["png_" + n].tobytes(), n
+        K.check_pin(n, first["png_" + n].tobytes())
 
 
 def test_save_image_pipelines_more_files_than_buffers(tmp_path):

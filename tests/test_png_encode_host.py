@@ -19,26 +19,16 @@ import host_child  # noqa: E402
 import png_encode_cases as K  # noqa: E402
 
 
-def host_seams(IW):
-    check = host_child.install_seams(IW, buffers="all")
-    IW._have_device = lambda: True
-    IW._to_device = lambda t, dev: t.clone()
-    return check
+host_seams = host_child.install_transfer_seams
 
 
 def _child(case, out):
-    import torch
     import image_writer as IW
     check = host_seams(IW)
 
     def up(t):
         return t.clone()
-
-    def alloc(nbytes):
-        return IW.torch.empty(int(nbytes), dtype=torch.uint8)
-
-    def down(t):
-        return t.detach().numpy().copy()
+    alloc, down = host_child.host_buffers(IW)
     kind, _, names = case.partition(":")
     res = {"cases": K.run_cases, "entry": K.run_entry}[kind](IW, up, alloc, down, names.split(",") if names else None)
     res["buffers"] = np.array(check())
@@ -55,7 +45,8 @@ def _emulate(case, tmp_path):
 def test_files_decode_to_torchs_bytes_and_streams_to_the_restated_scanlines(tmp_path, names):
     """every case: Pillow's decode equals torch's CPU arithmetic, the inflated IDAT payload equals the restated scanline stream, two
     encodes are identical, the stream is within the stored bound and (compressible cases of at least one block) within the derived
-    allowance over zlib's Z_RLE stream; the sizes are printed"""
+    allowance over zlib's Z_RLE stream, and the file is byte for byte the pinned one (tests/golden/png_encode_pins.json); the sizes are
+    printed"""
     pytest.importorskip("PIL")
     assert len(K.check_cases(_emulate("cases:" + ",".join(names), tmp_path), names)) == len(names)
 

@@ -14,47 +14,19 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import scene_images_cases as K  # noqa: E402
 import scene_images_runs as R  # noqa: E402
+from gpu_poison import Poisoned  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-PAD = 256
 REF = os.path.join(ROOT, "oracle", "_ref", "refpy")
-_held = []
+_mem = Poisoned()
+alloc, down, guards_intact = _mem.alloc, _mem.down, _mem.guards_intact
 _count = [0]
-
-
-def _inside(nbytes, offset):
-    import torch
-    whole = torch.full((offset + nbytes + PAD,), 0xA5, dtype=torch.uint8, device="cuda")
-    view = whole[offset:offset + nbytes]
-    _held.append((whole, view))
-    return view
 
 
 def up(a):
     import torch
-    a = np.ascontiguousarray(a)
     _count[0] += 1
-    view = _inside(a.nbytes, PAD + (_count[0] & 1))
-    view.copy_(torch.from_numpy(a.reshape(-1).copy()))
-    return view.reshape(a.shape)
-
-
-def alloc(nbytes):
-    return _inside(int(nbytes), PAD)
-
-
-def down(t):
-    return t.detach().cpu().numpy().copy()
-
-
-def guards_intact():
-    n = 0
-    for whole, view in _held:
-        off = view.data_ptr() - whole.data_ptr()
-        assert bool((whole[:off] == 0xA5).all()) and bool((whole[off + view.numel():] == 0xA5).all()), "bytes around a %d-byte tensor were overwritten" % view.numel()
-        n += 1
-    _held.clear()
-    return n
+    return _mem.up(torch.from_numpy(np.ascontiguousarray(a)), offset=_count[0] & 1)       # (every second source at an odd address)
 
 
 @pytest.fixture(scope="module")
@@ -65,7 +37,7 @@ def golden():
 def _run(case, tmp_path, guarded=True):
     import torch
     import scene_images as SI
-    _held.clear()
+    _mem.clear()
     res = R.RUNS[case](SI, up, alloc, down, str(tmp_path))
     torch.cuda.synchronize()
     assert guards_intact() > 0 or not guarded          # (the loader's run allocates everything itself)
@@ -90,7 +62,7 @@ def test_a_side_stream_gives_the_same_bits(tmp_path, golden):
     tags = ("odd", "wide", "rgba", "same")
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
-    _held.clear()
+    _mem.clear()
     with torch.cuda.stream(side):
         res = R.run_shapes(SI, up, alloc, down, str(tmp_path), tags=tags)
     side.synchronize()

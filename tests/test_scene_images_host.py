@@ -22,10 +22,7 @@ import scene_images_runs as R  # noqa: E402
 
 def host_seams(SI):
     """the stand-ins for scene_images' device seams -> check() of the guards"""
-    check = host_child.install_seams(SI, buffers="all")
-    SI._have_device = lambda: True
-    SI._pinned = lambda n: SI.torch.empty(n, dtype=SI.torch.uint8)
-    SI._to_device = lambda t, dev: t.clone()
+    check = host_child.install_transfer_seams(SI)
     SI._side_stream = lambda: None
     SI._side_waits_for_caller = lambda side: None
     SI._copy_on = lambda side, dst, src: dst.copy_(src)
@@ -42,12 +39,7 @@ def _child(case, out):
 
     def up(a):
         return torch.from_numpy(np.ascontiguousarray(a).copy())
-
-    def alloc(nbytes):
-        return SI.torch.empty(int(nbytes), dtype=torch.uint8)
-
-    def down(t):
-        return t.detach().numpy().copy()
+    alloc, down = host_child.host_buffers(SI)
     tmp = os.path.join(os.path.dirname(out), "files_" + case)
     os.makedirs(tmp, exist_ok=True)
     if case.startswith("shapes:"):
