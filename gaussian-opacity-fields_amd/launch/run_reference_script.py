@@ -97,6 +97,11 @@ What it does, in this order (nothing in the reference checkout is edited):
      (interlaced, not 8 bits, a palette, tRNS) goes through the script's own function, which run_script keeps (SCRIPT_OWN).  Its speed has
      not been measured on the device yet, so the binding is asked for (PNG_READER_BY_DEFAULT below); GOF_PIL_PNG_READ=1 leaves the script
      alone whatever else is set.  scene_images' decoding of PNG training images stays Pillow's.
+ 17. Opt-in only: GOF_MESH_COMPONENTS=<spec> (`largest:1`, `min_area_ratio:0.2,connectivity:vertex`; the keys are the keyword arguments of
+     DeviceMesh.keep_components) removes the small disconnected pieces of the extracted mesh (mesh_components.py, csrc/mesh_components.hip,
+     DESIGN.md 3.18).  The replacements of 9. and of extract_mesh_tsdf.py's `tsdf_fusion` first write the file they always wrote, byte for
+     byte; then that file is read back, reduced to the selected components and written next to it as mesh_binary_search_7_clean.ply /
+     tsdf_clean.ply.  A malformed spec is an error before the script starts.  Unset: nothing differs.
 """
 import importlib
 import os
@@ -566,6 +571,42 @@ def appearance_rebinding(script):
     return {"L1_loss_appearance": _l1_loss_appearance}
 
 
+def mesh_components_spec():
+    """GOF_MESH_COMPONENTS=<spec> -> the keyword arguments of DeviceMesh.keep_components, None where it is unset or empty; a malformed
+    spec raises ValueError (main() asks before the script starts)"""
+    spec = os.environ.get("GOF_MESH_COMPONENTS", "")
+    if not spec.strip():
+        return None
+    import mesh_components
+    return mesh_components.parse_spec(spec)
+
+
+# (the name rebound, the directory below <model_path>/<name>/ours_<iteration>, the file it writes, the file written next to it)
+CLEAN_MESH_FILES = (("marching_tetrahedra_with_binary_search", "fusion", "mesh_binary_search_7.ply", "mesh_binary_search_7_clean.ply"),
+                    ("tsdf_fusion", "tsdf", "tsdf.ply", "tsdf_clean.ply"))
+
+
+def _with_clean_mesh(fn, subdir, written, clean, criteria):
+    def run(model_path, name, iteration, *args, **kwargs):
+        out = fn(model_path, name, iteration, *args, **kwargs)       # (writes its file as always, first)
+        import mesh_components
+        folder = os.path.join(model_path, name, "ours_{}".format(iteration), subdir)
+        kept, dropped = mesh_components.clean_file(os.path.join(folder, written), os.path.join(folder, clean), **criteria)
+        print("mesh components: kept %d of %d -> %s" % (kept, kept + dropped, os.path.join(folder, clean)))
+        return out
+    return run
+
+
+def mesh_components_rebinding(rebind):
+    """the entries of `rebind` that write a mesh, wrapped so that the cleaned mesh is written next to theirs -- only where
+    GOF_MESH_COMPONENTS is set (17.); a name that is not rebound (GOF_TORCH_EXTRACT=1) is left alone"""
+    criteria = mesh_components_spec()
+    if criteria is None:
+        return {}
+    return {name: _with_clean_mesh(rebind[name], subdir, written, clean, criteria) for name, subdir, written, clean in CLEAN_MESH_FILES
+            if name in rebind}
+
+
 def _tnt_eval_main(argv):
     import tnt_eval
     return tnt_eval.main(argv)
@@ -647,6 +688,7 @@ def main():
     rebind.update(dtu_cull_rebinding(script))
     rebind.update(appearance_rebinding(script))
     rebind.update(png_reader_rebinding(script))
+    rebind.update(mesh_components_rebinding(rebind))
     try:
         run_script(script, rebind)
     except BaseException:

@@ -302,6 +302,44 @@ class DeviceMesh:
         with _device_of(m):
             self._f = _gather(_compact_rows(m), self._f)
 
+    # ---- connected components (mesh_components.py).  There is no split(): a list of 10^5 mesh objects is what these
+    # methods replace -- select with keep_components, or index with components().face_comp
+    def components(self, connectivity="edge"):
+        """-> mesh_components.Components: face_comp (M,) int32 on the device (components numbered in the order of their first face) and
+        the host arrays faces, area, first_face per component.  connectivity 'edge': faces sharing a pair of vertex indices hang
+        together; 'vertex': faces sharing a vertex index."""
+        import mesh_components
+        return mesh_components.components(self._v, self._f, connectivity)
+
+    @property
+    def area(self):
+        """the sum of the faces' areas: per component in the written order, the components added in ascending number"""
+        import mesh_components
+        return mesh_components.total_area(self.components().area)
+
+    def remove_unreferenced_vertices(self):
+        """trimesh's: drop the vertices no face refers to and renumber the faces; everything kept stays in its order"""
+        import mesh_components
+        self._apply(mesh_components.referenced_vertices(self._f, int(self._v.size(0))), True)
+
+    def keep_components(self, largest=None, by="faces", min_faces=None, min_area_ratio=None, connectivity="edge"):
+        """In place: keep the faces of the selected components and the vertices they still refer to (normals and colours follow),
+        everything in its original order -> (components kept, components dropped).  largest=k with by='faces'|'area' (ties: the
+        component whose first face comes first; a NaN area orders below every number), min_faces=n, min_area_ratio=r (area > r x
+        the total area: eval_tnt/cull_mesh.py:197); criteria given together are ANDed.  The component table goes to the host once and
+        is decided there; masks, marking and compaction run on the device."""
+        import mesh_components
+        comps = self.components(connectivity)
+        keep = mesh_components.select(comps.faces, comps.area, largest, by, min_faces, min_area_ratio)
+        if int(self._f.size(0)):
+            self.update_faces(mesh_components.component_mask(comps.face_comp, keep))
+        self.remove_unreferenced_vertices()
+        kept = int(keep.sum())
+        mesh_components._last["keep"] = {"components": len(keep), "kept": kept, "kept_faces": int(self._f.size(0)), "kept_vertices": int(self._v.size(0)),
+                                         "kept_mask": keep.tolist(), "comp_faces": comps.faces.tolist(), "comp_first": comps.first_face.tolist(),
+                                         "comp_area": comps.area.tolist()}
+        return kept, len(keep) - kept
+
     def export(self, path):
         """binary little-endian PLY: float x y z [nx ny nz] [uchar red green blue], `list uchar int` faces"""
         v = self._v.cpu().numpy()

@@ -3,7 +3,9 @@
  *
  * What the reference's evaluate_dtu_mesh.py:77-131 (cull_mesh) asks of scikit-image, torch GEMMs + grid_sample and trimesh:
  * (a) disk dilation of every view's object mask, (b) projection of every vertex into every view and the test against the dilated
- * masks, (c) compaction of the mesh to the kept vertices and the faces between them.
+ * masks, (c) compaction of the mesh to the kept vertices and the faces between them.  And what that script and
+ * eval_tnt/cull_mesh.py:186-201 leave disabled for want of a split() that scales: (d) the connected components of the mesh, their
+ * sizes, and the masks that drop the small ones (csrc/mesh_components.hip).
  *
  * Conventions as in gof_hip.h: extern "C", device pointers, caller-owned workspace with a *_bytes query whose contents do not
  * matter on entry, launches on `stream`, 0 = ok, negative = GOF_E_* with text in gof_last_error().  Every operation that decides
@@ -61,6 +63,50 @@ size_t gof_mesh_compact_ws_bytes(int64_t num_vertices, int64_t num_faces);
 int gof_mesh_compact(int64_t num_vertices, const uint8_t* keep, int64_t num_faces, const int32_t* faces, int32_t drop_faces,
                      int32_t* out_rows, int32_t* out_faces, uint8_t* face_keep, void* ws, size_t ws_bytes, int64_t* counts,
                      void* stream);
+
+/* ---- (d) connected components (csrc/mesh_components.hip) -----------------------------------------------------------
+ * faces [NF,3] int32 with indices in [0, NV), 3 * NF < 2^31.  mode GOF_MESH_CONN_EDGE: two faces are adjacent iff they share an
+ * unordered pair of vertex indices (however many faces lie on that pair); GOF_MESH_CONN_VERTEX: iff they share a vertex index.  A face
+ * with a repeated index takes part like any other; vertices are never merged by position.
+ * face_label [NF] int32: the smallest face index of the face's component.  face_comp [NF] int32: the rank of that index among all
+ * roots (components numbered 0 .. C-1 in the order of their first face).  *num_components (host) = C.  Both arrays are functions of
+ * `faces` alone.  An index outside [0, NV), 3 * NF >= 2^31 or an unknown mode is GOF_E_INVALID and nothing is written (the indices are
+ * checked by a launch of their own before any output is touched); a labelling that fails its own check (a united pair with different
+ * labels, a label that is not its own label) is GOF_E_DEVICE.  NF = 0 gives C = 0.  Waits for the stream (once for the index check,
+ * once per round of pointer jumping, once for C). */
+#define GOF_MESH_CONN_EDGE 0
+#define GOF_MESH_CONN_VERTEX 1
+int gof_mesh_abi_version(void);        /* 2: (a)-(c) were 1 */
+/* the sizes at which this unit changes its path, for tests: out[0] items per block of the radix sort, out[1] items per tile of the
+ * scan, out[2] positions per tile and out[3] per block of the area sums */
+void gof_mesh_components_tiling(int64_t* out);
+size_t gof_mesh_components_ws_bytes(int64_t num_vertices, int64_t num_faces, int32_t mode);
+int gof_mesh_components(int64_t num_vertices, int64_t num_faces, const int32_t* faces, int32_t mode, int32_t* face_label,
+                        int32_t* face_comp, int64_t* num_components, void* ws, size_t ws_bytes, void* stream);
+
+/* Per component c of face_comp [NF] (values in [0, C); a component without a face is allowed):
+ * comp_faces [C] int64: its number of faces; comp_first [C] int32: its smallest face index (-1 without a face); comp_area [C] fp64.
+ * The area of a face (vertices [NV,3] fp64), every operation IEEE fp64 in this order, nothing contracted:
+ *   e1 = v1 - v0, e2 = v2 - v0;  cx = e1y e2z - e1z e2y, cy = e1z e2x - e1x e2z, cz = e1x e2y - e1y e2x;
+ *   a = 0.5 * sqrt((cx cx + cy cy) + cz cz).
+ * The sum of a component: the faces stably sorted by component (ascending face index inside a component) form one sequence; position p
+ * of that sequence lies in tile p / 256 and in block p / 65536.  The areas of a component inside one tile are added from left to
+ * right, starting from the first; the tile sums inside one block are added from left to right; the block sums are added from left to
+ * right.  No floating-point atomics: the result has the same bits on every run.  A component without a face has area 0.
+ * An index outside [0, NV) or a face_comp outside [0, C) is GOF_E_INVALID, checked before any output is written. */
+size_t gof_mesh_component_stats_ws_bytes(int64_t num_faces, int64_t num_components);
+int gof_mesh_component_stats(int64_t num_vertices, int64_t num_faces, const double* vertices, const int32_t* faces,
+                             const int32_t* face_comp, int64_t num_components, int64_t* comp_faces, int32_t* comp_first,
+                             double* comp_area, void* ws, size_t ws_bytes, void* stream);
+
+/* face_keep [NF] uint8 = comp_keep[face_comp[f]] != 0 (comp_keep [C] uint8; a face_comp outside [0, C) gives 0).  No workspace. */
+int gof_mesh_component_mask(int64_t num_faces, const int32_t* face_comp, int64_t num_components, const uint8_t* comp_keep,
+                            uint8_t* face_keep, void* stream);
+
+/* vert_keep [NV] uint8 = 1 iff some face f with face_keep[f] != 0 (face_keep = NULL: every face) has the vertex among its indices.
+ * Indices outside [0, NV) mark nothing (gof_mesh_compact refuses them).  No workspace, no wait. */
+int gof_mesh_mark_referenced(int64_t num_vertices, int64_t num_faces, const int32_t* faces, const uint8_t* face_keep,
+                             uint8_t* vert_keep, void* stream);
 
 #ifdef __cplusplus
 }
