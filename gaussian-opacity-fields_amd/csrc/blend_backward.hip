@@ -15,6 +15,8 @@
 //         s_slab[wave][16][BATCH]: a wave visits an entry at most once per batch, so nothing is read back and no LDS
 //         atomic is needed (measured: ds_add_f32 costs ~3.5 cycles per active LANE; the former 68 lane-atomics per
 //         entry and wave kept the LDS busy ~70 % of the time);
+//      (two consecutive visited entries with disjoint lanes share ONE such trip -- each lane evaluates its own entry, the reader lanes
+//      form both totals from the one panel, two slab columns are stored: GOF_BW_MERGE below, with the order argument)
 //      4. after the batch, thread j adds the slabs of the waves that visited entry j (in wave order) and STORES the 16 sums as
 //         the partial gradient of that (tile, Gaussian) instance -- plain stores into a 64-byte record (one line) of a POOL (one record per
 //         staged instance; a wave takes its batch's slots with one atomic on the pool's cursor), whose slot + 1 goes into a word
@@ -70,6 +72,16 @@ static_assert(BATCH == 32 || BATCH == 64 || BATCH == 128, "BATCH must be 32, 64 
 // profiles/r05_ab_call6_binning.txt -- with five workgroups per CU resident the idle waves at the staging barrier cost nothing another
 // workgroup cannot use; removed in round 6).
 constexpr int RED_STRIDE = 68;
+// Two consecutive visited entries of a wave whose contributing lanes are DISJOINT share one trip (GOF_BW_MERGE=0 builds the walk
+// without it: lib/libgof_hip_nomerge.so, the partner of tests/test_backward_merge_gpu.py): every lane runs the gradient block for its
+// own entry, all 64 lanes store into the panel once, and the reader lanes form TWO totals from the same eight values, each with +0.0f
+// selected in place of the lanes of the other entry.  Order argument: a lane only ever works on entries its own mask bits name, and it
+// still meets them in descending list position -- it contributes to at most one of the two, and nothing of its own lies between them --
+// so T, acc01, acc2n, accn01 see the same operands in the same order; a total is the same ordered sum over the same 64 operands (the
+// lanes without a contribution to THAT entry give +0.0f, as they do in a trip of their own).  Every gradient keeps its bits.
+#ifndef GOF_BW_MERGE
+#define GOF_BW_MERGE 1
+#endif
 #ifdef GOF_STATS
 // developer-only instrumentation (never in the shipped build): [0] wave iterations of the entry loop, [1] (row, iteration) pairs with
 // an entry to visit, [2] contributing (lane, entry) pairs, [3] word fetches, [4] staged entries, [5] pairs of CONSECUTIVE visited
@@ -77,7 +89,9 @@ constexpr int RED_STRIDE = 68;
 // block could save), [6] (row, entry) pairs with at least one contributing lane (a walk per 16-lane row would visit those),
 // [7] visited entries in which at most 32 lanes contribute, [8] sum over the batches of the LARGEST visit count among the tile's four
 // waves (what the batch's barriers make every wave wait for), [9] batches, [10] sum over the tiles of the largest per-tile visit total
-// among the four waves (what the tile would take if its waves ran without the batch barriers)
+// among the four waves (what the tile would take if its waves ran without the batch barriers), [11] trips that carried two entries
+// (GOF_BW_MERGE: equals [5], the same greedy rule); with -DGOF_BW_COUNT_LOOKAHEAD instead what a bounded look-ahead would save: B may be
+// any of the next three unmerged entries of the word whose lanes are disjoint from A's and from every entry skipped on the way to it
 __device__ unsigned long long g_bw_stats[12];
 #define BSTAT_ADD(i, v) atomicAdd(&g_bw_stats[i], (unsigned long long)(v))
 #else
@@ -302,25 +316,74 @@ blend_backward_tile(const uint32_t tile, const uint2* __restrict__ ranges, const
                 const int c2 = __popc((uint32_t)__builtin_amdgcn_readlane((int)ru, 32)), c3 = __popc((uint32_t)__builtin_amdgcn_readlane((int)ru, 48));
                 if (lane == 0) { BSTAT_ADD(1, max(max(c0, c1), max(c2, c3))); BSTAT_ADD(3, __popc(todo)); }
             }
+#ifdef GOF_BW_COUNT_LOOKAHEAD
+            {   // [11] what a bounded look-ahead would save in this word (a count only: the walk below is not changed by it)
+                unsigned long long sets[32];
+                int ns = 0;
+                for (uint32_t t = todo; t; ) { const int bb = 31 - __builtin_clz(t); t &= ~(1u << bb); sets[ns++] = __ballot((word >> bb) & 1u); }
+                if (lane == 0) {
+                    uint32_t used = 0u, saved = 0u;
+                    for (int i = 0; i < ns; i++) {
+                        if (used >> i & 1u) continue;
+                        unsigned long long busy = sets[i];             // A's lanes and those of the entries skipped so far
+                        for (int k = i + 1, seen = 0; k < ns && seen < 3; k++) {
+                            if (used >> k & 1u) continue;
+                            seen++;
+                            if ((sets[k] & busy) == 0ull) { used |= 1u << k; saved++; break; }
+                            busy |= sets[k];
+                        }
+                    }
+                    BSTAT_ADD(11, saved);
+                }
+            }
+#endif
 #endif
             while (todo) {
                 const int b = 31 - __builtin_clz(todo);
                 todo &= ~(1u << b);
-                const bool contrib = (word >> b) & 1u;
+                bool contrib = (word >> b) & 1u;
                 const int j = w * 32 + b;
-                const uint32_t contributor = p0 + (uint32_t)j;       // 0-based list position (backward.cu:763)
+                int jj = j;                                          // the lane's own entry of this trip
                 if (lane == 0) BSTAT_ADD(0, 1);
+#if GOF_BW_MERGE || defined(GOF_STATS)
+                const unsigned long long set_a = __ballot(contrib);
+#endif
 #ifdef GOF_STATS
-                {
-                    const unsigned long long cur_set = __ballot(contrib);
+                auto stat_entry = [&](const unsigned long long cur_set) {
                     if (lane == 0) {
                         if (stat_prev_set != 0ull && (stat_prev_set & cur_set) == 0ull) { BSTAT_ADD(5, 1); stat_prev_set = 0ull; }   // merged: neither pairs again
                         else stat_prev_set = cur_set;
                         BSTAT_ADD(6, ((cur_set & 0xFFFFull) != 0) + ((cur_set & 0xFFFF0000ull) != 0) + ((cur_set & 0xFFFF00000000ull) != 0) + ((cur_set >> 48) != 0));
                         if (__popcll(cur_set) <= 32) BSTAT_ADD(7, 1);
                     }
+                };
+                stat_entry(set_a);
+#endif
+#if GOF_BW_MERGE
+                // the next visited entry of the word rides in this trip if its lanes are disjoint from this one's (wave-uniform: two
+                // ballots and a scalar test; j2 < 0: a trip of one entry, everything below as it was without merging)
+                int j2 = -1;
+                unsigned long long set_b = 0ull;
+                if (todo) {
+                    const int b2 = 31 - __builtin_clz(todo);
+                    const bool contrib_b = (word >> b2) & 1u;
+                    set_b = __ballot(contrib_b);
+                    if ((set_a & set_b) == 0ull) {
+                        todo &= ~(1u << b2);
+                        j2 = w * 32 + b2;
+                        if (contrib_b) jj = j2;
+                        contrib |= contrib_b;
+                        if (lane == 0) BSTAT_ADD(0, 1);
+#ifndef GOF_BW_COUNT_LOOKAHEAD
+                        if (lane == 0) BSTAT_ADD(11, 1);
+#endif
+#ifdef GOF_STATS
+                        stat_entry(set_b);
+#endif
+                    }
                 }
 #endif
+                const uint32_t contributor = p0 + (uint32_t)jj;      // 0-based list position (backward.cu:763)
 
                 float g[NGRAD];
                 // (Measured and dropped, round 4: EVERY lane running the gradient block with alpha = G = 0 and harmless stand-ins for a
@@ -329,9 +392,10 @@ blend_backward_tile(const uint32_t tile, const uint2* __restrict__ ranges, const
                 // 1.067 ms at S1M, 1.379 vs 1.364 ms clustered: no difference.  profiles/r04_ab_call5_*.txt)
 #pragma unroll
                 for (int k = 0; k < NGRAD; k++) g[k] = 0.f;
+                // the gradient block of the lane's (pixel, entry) pair -- the wave's one entry, or in a merged trip the lane's own of the two
                 if (contrib) {
                     BSTAT_ADD(2, 1);
-                    const f4 q0 = s_rec[0][j], q1 = s_rec[1][j], q2 = s_rec[2][j], q3 = s_rec[3][j], q4 = s_rec[4][j], q5 = s_rec[5][j];
+                    const f4 q0 = s_rec[0][jj], q1 = s_rec[1][jj], q2 = s_rec[2][jj], q3 = s_rec[3][jj], q4 = s_rec[4][jj], q5 = s_rec[5][jj];
                     // fp32 prelude in the forward's operation order (min_value is ill-conditioned in it), two values per instruction
                     const f2 n01 = (q0.xy * RX + q0.zw * RY) + q1.xy;               // normal[0], normal[1]
                     const f2 n2b = (q1.zw * RX + q2.xy * RY) + q2.zw;               // normal[2], BB / 2
@@ -434,6 +498,49 @@ blend_backward_tile(const uint32_t tile, const uint2* __restrict__ ranges, const
                     // formed from the total of g[6] at the flush, not reduced here
                     }
                 }
+#if GOF_BW_MERGE
+                if (j2 >= 0) {
+                    // Two entries in the panel.  The reader lane (v, p) holds lanes 8 p .. 8 p + 7 of value v: their bits of set_b say whose
+                    // value each is.  A lane outside both entries stored +0.0f, so one bit decides both totals: entry A's takes the values
+                    // whose bit is clear, entry B's those whose bit is set, +0.0f in the other's place (a select, not a product with 0 / 1:
+                    // that could leave -0.0f) -- the operands, and the association below, of each entry's own trip.
+                    float* const panel = &s_red[wave][0][0];
+                    const uint32_t of_b = (uint32_t)(set_b >> (8u * (lane & 7u))) & 0xffu;
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+#pragma unroll
+                        for (int k = 0; k < NGRAD / 2; k++) panel[k * RED_STRIDE + lane] = g[h * (NGRAD / 2) + k];
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        const f4* const rp = reinterpret_cast<const f4*>(panel + (lane >> 3) * RED_STRIDE + 8u * (lane & 7u));
+                        const f4 a = rp[0], b = rp[1];
+                        const float x[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+                        float xa[8], xb[8];
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            const bool is_b = (of_b >> i) & 1u;
+                            xa[i] = is_b ? 0.f : x[i];
+                            xb[i] = is_b ? x[i] : 0.f;
+                        }
+                        float tot_a = ((xa[0] + xa[1]) + (xa[2] + xa[3])) + ((xa[4] + xa[5]) + (xa[6] + xa[7]));
+                        float tot_b = ((xb[0] + xb[1]) + (xb[2] + xb[3])) + ((xb[4] + xb[5]) + (xb[6] + xb[7]));
+                        tot_a = tot_a + dpp_get<0xB1>(tot_a);         // quad_perm [1,0,3,2]
+                        tot_b = tot_b + dpp_get<0xB1>(tot_b);
+                        tot_a = tot_a + dpp_get<0x4E>(tot_a);         // quad_perm [2,3,0,1]
+                        tot_b = tot_b + dpp_get<0x4E>(tot_b);
+                        tot_a = tot_a + dpp_get<0x141>(tot_a);        // row_half_mirror: the other quad of the 8 lanes
+                        tot_b = tot_b + dpp_get<0x141>(tot_b);
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        if ((lane & 7u) == 0u) {
+                            s_slab[wave][h * (NGRAD / 2) + (lane >> 3)][j] = tot_a;
+                            s_slab[wave][h * (NGRAD / 2) + (lane >> 3)][j2] = tot_b;
+                        }
+                    }
+                    continue;
+                }
+#endif
                 // The wave's own panel: no other wave touches it, and the LDS serves a wave's instructions in order -- the wave
                 // barriers only keep the compiler from moving the accesses across (no instruction).
                 {
