@@ -102,6 +102,13 @@ What it does, in this order (nothing in the reference checkout is edited):
      DESIGN.md 3.18).  The replacements of 9. and of extract_mesh_tsdf.py's `tsdf_fusion` first write the file they always wrote, byte for
      byte; then that file is read back, reduced to the selected components and written next to it as mesh_binary_search_7_clean.ply /
      tsdf_clean.ply.  A malformed spec is an error before the script starts.  Unset: nothing differs.
+ 18. eval_tnt/cull_mesh.py asks pyrender (OpenGL over EGL) for a depth image of the mesh per camera and torch for the views that see each
+     vertex in front of it: for a script that defines both `Mesher` and `extract_depth_from_mesh` the two names become
+     mesh_cull.TntMesher and mesh_cull.render_depth (csrc/mesh_raster.hip, DESIGN.md 3.19: a triangle rasteriser with a z-buffer and the
+     per-vertex count over it, a batch of views at a time), rebound as 6. rebinds `evaluage_alpha`; the script's __main__, its get_traj
+     and its intrinsics run as they are.  `import pyrender` resolves to the stand-in of shims/ where pyrender is not installed, open3d,
+     trimesh and cv2 to theirs (2., 10., 13.).  The mesh that is culled is the file the script is given (its own
+     extract_depth_from_mesh loads a file of its author's, :28).  GOF_TNT_CULL_TORCH=1 leaves the script alone.
 """
 import importlib
 import os
@@ -323,7 +330,7 @@ def add_cv2_stand_in():
 
 def add_import_stand_ins():
     """shims/ goes LAST on sys.path when one of the packages it stands in for is not importable: tetranerf and open3d (2., 6.),
-    lpips and torchvision (11.) and plyfile (13.).  An installed package comes earlier on the path and wins; lpips and plyfile are
+    lpips and torchvision (11.), plyfile (13.) and pyrender (18.).  An installed package comes earlier on the path and wins; lpips and plyfile are
     looked up without importing them (the real lpips imports torchvision's models at import)."""
     import importlib.util
     shim = os.path.join(PKG, "shims")
@@ -333,7 +340,7 @@ def add_import_stand_ins():
             importlib.import_module(mod)
         except Exception:
             missing = True
-    for mod in ("lpips", "torchvision", "plyfile"):
+    for mod in ("lpips", "torchvision", "plyfile", "pyrender"):
         try:
             missing = missing or importlib.util.find_spec(mod) is None
         except (ImportError, ValueError):
@@ -607,6 +614,34 @@ def mesh_components_rebinding(rebind):
             if name in rebind}
 
 
+def _tnt_mesher(*args, **kwargs):
+    import mesh_cull
+    return mesh_cull.TntMesher(*args, **kwargs)
+
+
+def _tnt_render_depth(mesh, c2w_list, H, W, fx, fy, cx, cy, far=20.0):
+    import mesh_cull
+    return list(mesh_cull.render_depth(mesh, c2w_list, H, W, fx, fy, cx, cy, zfar=far))
+
+
+def tnt_cull_rebinding(script):
+    """the names to replace in `script`'s namespace for the Tanks-and-Temples mesh culling (18.): `Mesher` and
+    `extract_depth_from_mesh`, for a script that defines both (eval_tnt/cull_mesh.py).  The replacements import mesh_cull when they are
+    called, not here."""
+    import ast
+    if os.environ.get("GOF_TNT_CULL_TORCH", "0") == "1" or not os.path.isfile(script):
+        return {}
+    with open(script, "rb") as f:
+        try:
+            tree = ast.parse(f.read(), filename=script)
+        except SyntaxError:
+            return {}
+    defined = {n.name for n in tree.body if isinstance(n, (ast.FunctionDef, ast.ClassDef))}
+    if not {"Mesher", "extract_depth_from_mesh"} <= defined:
+        return {}
+    return {"Mesher": _tnt_mesher, "extract_depth_from_mesh": _tnt_render_depth}
+
+
 def _tnt_eval_main(argv):
     import tnt_eval
     return tnt_eval.main(argv)
@@ -688,6 +723,7 @@ def main():
     rebind.update(dtu_cull_rebinding(script))
     rebind.update(appearance_rebinding(script))
     rebind.update(png_reader_rebinding(script))
+    rebind.update(tnt_cull_rebinding(script))
     rebind.update(mesh_components_rebinding(rebind))
     try:
         run_script(script, rebind)
@@ -721,7 +757,7 @@ def run_script(script, rebind):
     with open(script, "rb") as f:
         src = f.read()
     tree = ast.parse(src, filename=script)
-    defined = {n.name for n in tree.body if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef))}
+    defined = {n.name for n in tree.body if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef))}      # (a class: 18.'s Mesher)
     # (and the modules it imports under their own name at top level: evaluate_dtu_mesh.py's `import os`)
     defined |= {a.asname or a.name for n in tree.body if isinstance(n, ast.Import) for a in n.names if "." not in (a.asname or a.name)}
     names = [k for k in rebind if k in defined]

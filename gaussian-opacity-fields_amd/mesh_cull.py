@@ -340,6 +340,17 @@ class DeviceMesh:
                                          "comp_area": comps.area.tolist()}
         return kept, len(keep) - kept
 
+    def cull_by_visibility(self, c2w_list, H, W, fx, fy, cx, cy, zfar=20.0, eps=0.005, min_views=20, znear=0.01, convention="opengl", batch=0):
+        """eval_tnt/cull_mesh.py:220-249 in place: a depth image of this mesh per camera, the views that see each vertex in front of it,
+        then update_faces(every vertex seen by at least min_views) and remove_unreferenced_vertices -> the per-vertex counts (before
+        the compaction), on the device"""
+        count, keep = visibility(self, c2w_list, H, W, fx, fy, cx, cy, znear=znear, zfar=zfar, eps=eps, min_views=min_views,
+                                 convention=convention, batch=batch)
+        out = compact_mesh(keep, self._f)
+        self.update_faces(out["face_keep"])
+        self.remove_unreferenced_vertices()
+        return count
+
     def export(self, path):
         """binary little-endian PLY: float x y z [nx ny nz] [uchar red green blue], `list uchar int` faces"""
         v = self._v.cpu().numpy()
@@ -452,3 +463,258 @@ def load_dtu_camera(DTU):
         pose[:3, 3] = centre
         poses.append(pose[:3])
     return poses
+
+
+# ---- eval_tnt/cull_mesh.py: depth rasteriser and visibility cull (csrc/mesh_raster.hip) -----------------------------
+class GofRasterView(C.Structure):
+    """Mirror of ``GofRasterView`` in include/gof_mesh_hip.h."""
+    _fields_ = [("w2c", C.c_double * 12), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("znear", C.c_double), ("zfar", C.c_double), ("W", C.c_int32), ("H", C.c_int32)]
+
+
+_RASTER_DTYPE = np.dtype([("w2c", "<f8", (12,)), ("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8"), ("znear", "<f8"), ("zfar", "<f8"),
+                          ("W", "<i4"), ("H", "<i4")])
+assert _RASTER_DTYPE.itemsize == C.sizeof(GofRasterView) == 152
+
+_f64 = C.c_double
+lib.gof_mesh_raster_abi_version.restype = C.c_int
+lib.gof_mesh_raster_abi_version.argtypes = []
+lib.gof_mesh_raster_tiling.restype = None
+lib.gof_mesh_raster_tiling.argtypes = [_P64]
+gn.bind(lib, {"gof_mesh_render_depth_ws_bytes": [_i64], "gof_mesh_visibility_ws_bytes": [_i64, _i64, _i32]}, {
+        "gof_mesh_render_depth": [_i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _P64, _vp, _sz, _vp],
+        "gof_mesh_visible_count": [_i64, _vp, _i32, _vp, _i64, _vp, _f64, _vp, _vp, _sz, _vp],
+        "gof_mesh_visibility": [_i64, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _f64, _i32, _vp, _vp, _P64, _vp, _sz, _vp]})
+
+_STAT_NAMES = ("triangles", "listed", "refused_by_full_list", "atomics", "pixels")
+__all__ += ["GofRasterView", "raster_tiling", "raster_views", "render_depth", "visible_count", "visibility", "TntMesher", "get_traj", "main"]
+
+
+def raster_tiling():
+    """The sizes at which the rasteriser changes its path (gof_mesh_raster_tiling)."""
+    out = (C.c_int64 * 8)()
+    lib.gof_mesh_raster_tiling(out)
+    return dict(zip(("inline_max", "tile_w", "tile_h", "guard", "max_side", "batch", "list_min", "stripes"), (int(v) for v in out)))
+
+
+def raster_views(c2w_list, H, W, fx, fy, cx, cy, znear=0.01, zfar=20.0, convention="opengl"):
+    """The view records of a camera list: c2w (4,4) or (3,4), tensors or arrays; convention 'opengl' (the camera looks down -z, +y is
+    up: what eval_tnt/cull_mesh.py hands to pyrender) or 'opencv' (+z forward, +y down).  World-to-camera is the fp64 inverse of the
+    OpenCV camera-to-world, formed here on the host."""
+    if convention not in ("opengl", "opencv"):
+        raise ValueError("raster_views: convention must be 'opengl' or 'opencv', got %r" % (convention,))
+    rec = np.zeros(len(c2w_list), _RASTER_DTYPE)
+    for i, c2w in enumerate(c2w_list):
+        if isinstance(c2w, torch.Tensor):
+            c2w = c2w.detach().cpu().numpy()
+        m = np.eye(4)
+        a = np.asarray(c2w, np.float64)
+        if a.shape not in ((4, 4), (3, 4)):
+            raise ValueError("raster_views: camera %d: expected a (4,4) or (3,4) camera-to-world matrix, got %s" % (i, a.shape))
+        m[:a.shape[0]] = a
+        if convention == "opengl":
+            m[:3, 1:3] *= -1.0
+        rec[i] = (np.linalg.inv(m)[:3].reshape(12), float(fx), float(fy), float(cx), float(cy), float(znear), float(zfar), int(W), int(H))
+    return rec
+
+
+def _mesh_arrays(mesh, who, need_faces=True):
+    """-> (vertices (NV,3) float32, faces (NF,3) int32 or None) on the device, of a DeviceMesh, a vertex tensor, or any object with
+    .vertices / .faces host arrays (a trimesh.Trimesh)"""
+    if isinstance(mesh, DeviceMesh):
+        return mesh._v.float().contiguous(), mesh._f
+    if isinstance(mesh, torch.Tensor):
+        if need_faces:
+            raise RuntimeError("%s: needs a mesh, got a tensor" % who)
+        return _tensor(mesh, who, "vertices", (torch.float32, torch.float64), 3).float().contiguous(), None
+    dev = _device()
+    v = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.vertices), np.float32).reshape(-1, 3)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.faces), np.int32).reshape(-1, 3)).to(dev)
+    return v, f
+
+
+def _records(rec, dev):
+    return torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(dev) if len(rec) else None
+
+
+def _stats(out, on):
+    return dict(zip(_STAT_NAMES, (int(v) for v in out))) if on else {}
+
+
+def render_depth(mesh, c2w_list, H, W, fx, fy, cx, cy, znear=0.01, zfar=20.0, convention="opengl", stats=False):
+    """eval_tnt/cull_mesh.py:17-66 (extract_depth_from_mesh) without pyrender: the depth of the mesh IT IS GIVEN from every camera ->
+    (N,H,W) float32 on the device, 0 where nothing is seen; both face orientations are drawn (SKIP_CULL_FACES)."""
+    v, f = _mesh_arrays(mesh, "render_depth")
+    rec = raster_views(c2w_list, H, W, fx, fy, cx, cy, znear, zfar, convention)
+    H, W, n, nv, nf = int(H), int(W), len(rec), int(v.size(0)), int(f.size(0))
+    with _device_of(v):
+        nb = lib.gof_mesh_render_depth_ws_bytes(nf)
+        ws = torch.empty(nb, dtype=torch.uint8, device=v.device)
+        depth = torch.empty((n, max(H, 0), max(W, 0)), dtype=torch.float32, device=v.device)
+        st = (C.c_int64 * 8)()
+        records = _records(rec, v.device)
+        B._check(lib.gof_mesh_render_depth(nv, _ptr(v), nf, _ptr(f), n, _ptr(records), max(H, 0) * max(W, 0), _ptr(depth),
+                                           st if stats else None, ws.data_ptr(), nb, _stream()))
+    _last["render_depth"] = dict({"vertices": nv, "faces": nf, "views": n, "workspace_bytes": int(nb)}, **_stats(st, stats))
+    return depth
+
+
+def visible_count(mesh_or_vertices, c2w_list, H, W, fx, fy, cx, cy, depth=None, znear=0.01, zfar=20.0, eps=0.005, convention="opengl", batch=0):
+    """Mesher.point_masks (:117-175) in fp64: per vertex the number of views that see it in front of the depth image -> (NV,) int32 on
+    the device.  depth (N,H,W) float32 given: the vertices (a tensor or a mesh) against those images; depth None: the images are
+    rendered from the mesh itself, a batch of views at a time (visibility)."""
+    if depth is None:
+        return visibility(mesh_or_vertices, c2w_list, H, W, fx, fy, cx, cy, znear=znear, zfar=zfar, eps=eps, min_views=0, convention=convention, batch=batch)[0]
+    v, _ = _mesh_arrays(mesh_or_vertices, "visible_count", need_faces=False)
+    rec = raster_views(c2w_list, H, W, fx, fy, cx, cy, znear, zfar, convention)
+    d = _tensor(depth, "visible_count", "depth", (torch.float32,))
+    if tuple(d.shape) != (len(rec), int(H), int(W)) or d.device != v.device:
+        raise RuntimeError("visible_count: depth must be (%d, %d, %d) on the vertices' device" % (len(rec), int(H), int(W)))
+    nv = int(v.size(0))
+    with _device_of(v):
+        nb = lib.gof_mesh_render_depth_ws_bytes(0)
+        ws = torch.empty(nb, dtype=torch.uint8, device=v.device)
+        count = torch.zeros(nv, dtype=torch.int32, device=v.device)
+        records = _records(rec, v.device)
+        B._check(lib.gof_mesh_visible_count(nv, _ptr(v), len(rec), _ptr(records), int(H) * int(W), _ptr(d), float(eps), _ptr(count),
+                                            ws.data_ptr(), nb, _stream()))
+    _last["visible_count"] = {"vertices": nv, "views": len(rec), "workspace_bytes": int(nb)}
+    return count
+
+
+def visibility(mesh, c2w_list, H, W, fx, fy, cx, cy, znear=0.01, zfar=20.0, eps=0.005, min_views=20, convention="opengl", batch=0, stats=False):
+    """Render and count, `batch` views at a time (0: the library's default): the depth images of all views never exist at once ->
+    (count (NV,) int32, keep (NV,) bool = count >= min_views) on the device."""
+    v, f = _mesh_arrays(mesh, "visibility")
+    rec = raster_views(c2w_list, H, W, fx, fy, cx, cy, znear, zfar, convention)
+    nv, nf, stride = int(v.size(0)), int(f.size(0)), max(int(H), 0) * max(int(W), 0)
+    with _device_of(v):
+        nb = lib.gof_mesh_visibility_ws_bytes(nf, stride, int(batch))
+        if nb == 0:
+            raise RuntimeError("visibility: bad batch (%d) or image size (%d x %d)" % (int(batch), int(W), int(H)))
+        ws = torch.empty(nb, dtype=torch.uint8, device=v.device)
+        count = torch.empty(nv, dtype=torch.int32, device=v.device)
+        keep = torch.empty(nv, dtype=torch.uint8, device=v.device)
+        st = (C.c_int64 * 8)()
+        records = _records(rec, v.device)
+        B._check(lib.gof_mesh_visibility(nv, _ptr(v), nf, _ptr(f), len(rec), _ptr(records), stride, int(batch), float(eps), int(min_views),
+                                         _ptr(count), _ptr(keep), st if stats else None, ws.data_ptr(), nb, _stream()))
+    _last["visibility"] = dict({"vertices": nv, "faces": nf, "views": len(rec), "batch": int(batch) or raster_tiling()["batch"], "workspace_bytes": int(nb)},
+                               **_stats(st, stats))
+    return count, keep.bool()
+
+
+class TntMesher:
+    """eval_tnt/cull_mesh.py's Mesher: the same constructor and __call__(mesh_path, c2w_list), writing <mesh>_cull.ply.  The mesh is the
+    file it is given (the script's extract_depth_from_mesh renders a file of its author's instead, :28), its vertices are never merged
+    by position (no merge_vertices / process=True).  components=<DeviceMesh.keep_components keyword arguments> adds the step the script
+    leaves commented out (:256).  forecast_radius is 0 as in the script; anything else needs Open3D's oriented bounding box."""
+
+    def __init__(self, H, W, fx, fy, cx, cy, far, points_batch_size=5e5, components=None):
+        self.points_batch_size = int(points_batch_size)
+        self.scale = 1.0
+        self.forecast_radius = 0
+        self.H, self.W, self.fx, self.fy, self.cx, self.cy = H, W, fx, fy, cx, cy
+        self.far = far
+        self.eps = 0.005
+        self.min_views = 20
+        self.remove_small_geometry_threshold = 0.2
+        self.get_largest_components = True
+        self.components = components
+        self.verbose = True
+
+    def cull_mesh(self, mesh, estimate_c2w_list):
+        """:204-289 -> (cull_mesh, forecast_mesh): the mesh is culled in place and is both"""
+        if abs(self.forecast_radius) > 0:
+            raise NotImplementedError("TntMesher: forecast_radius != 0 needs Open3D's oriented bounding box (eval_tnt/cull_mesh.py:261-283)")
+        mesh.cull_by_visibility(estimate_c2w_list, self.H, self.W, self.fx, self.fy, self.cx, self.cy, zfar=20.0, eps=self.eps, min_views=self.min_views)
+        if self.components is not None:
+            mesh.keep_components(**self.components)
+        return mesh, mesh
+
+    def __call__(self, mesh_path, estimate_c2w_list):
+        if abs(self.forecast_radius) > 0:
+            raise NotImplementedError("TntMesher: forecast_radius != 0 needs Open3D's oriented bounding box (eval_tnt/cull_mesh.py:261-283)")
+        mesh = load(mesh_path)
+        out = mesh_path.replace(".ply", "_cull.ply")
+        culled, _ = self.cull_mesh(mesh, estimate_c2w_list)
+        culled.export(out)
+        if self.verbose:
+            print("\nINFO: Save mesh at {}!\n".format(out))
+        return out
+
+
+def _orient_up_and_center(poses):
+    """nerfstudio's auto_orient_and_center_poses(method='up', center_poses=True) as eval_tnt/help_func.py:33-88 applies it, in numpy
+    float32: the mean up vector (column 1) is rotated onto +z and the mean camera position moved to the origin -> (N,3,4)"""
+    poses = np.asarray(poses, np.float32)
+    mean_t = poses[:, :3, 3].mean(axis=0, dtype=np.float32)
+    up = poses[:, :3, 1].mean(axis=0, dtype=np.float32)
+    a = up / np.linalg.norm(up)
+    a = a / np.linalg.norm(a)
+    b = np.array([0, 0, 1], np.float32)
+    v = np.cross(a, b).astype(np.float32)
+    c = np.float32(np.dot(a, b))
+    if c < -1 + 1e-8:
+        raise ValueError("get_traj: the cameras' mean up vector points along -z exactly: the reference perturbs it at random here")
+    s = np.float32(np.linalg.norm(v))
+    k = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]], np.float32)
+    rot = (np.eye(3, dtype=np.float32) + k + k @ k * np.float32((1 - c) / (s ** 2 + 1e-8))).astype(np.float32)
+    transform = np.concatenate([rot, rot @ -mean_t[:, None]], axis=-1).astype(np.float32)
+    return transform @ poses
+
+
+def get_traj(traj_path):
+    """eval_tnt/cull_mesh.py:321-363 through numpy: a .npy of camera-to-world matrices, or a transforms .json (instant-ngp / sdfstudio),
+    oriented, centred and scaled as the script does -> a list of (4,4) float32 tensors"""
+    traj = []
+    if traj_path.endswith(".npy"):
+        traj = [m for m in np.load(traj_path)]
+    elif traj_path.endswith(".json"):
+        import json
+        with open(traj_path, encoding="UTF-8") as fh:
+            meta = json.load(fh)
+        by_index = {int(frame["file_path"][13:18]) - 1: np.array(frame["transform_matrix"]) for frame in meta["frames"]}
+        poses = np.array([by_index[i] for i in range(len(by_index))]).astype(np.float32)
+        poses = _orient_up_and_center(poses)
+        poses[:, :3, 3] *= np.float32(1.0 / float(np.max(np.abs(poses[:, :3, 3]))))
+        traj = [m for m in poses]
+    out = []
+    for m in traj:
+        c2w = torch.from_numpy(np.ascontiguousarray(m)).float()
+        if tuple(c2w.shape) == (3, 4):
+            c2w = torch.cat([c2w, torch.tensor([[0, 0, 0, 1]]).float()], dim=0)
+        out.append(c2w)
+    return out
+
+
+# the script's Tanks-and-Temples intrinsics (eval_tnt/cull_mesh.py:387-392)
+TNT_INTRINSICS = {"height": 1080, "width": 1920, "fx": 1163.8678928442187, "fy": 1172.793101201448, "cx": 962.3120628412543, "cy": 542.0667209577691}
+
+
+def main(argv=None):
+    """python -m mesh_cull tnt --traj-path T --ply-path P: the script's __main__ (:366-399)"""
+    import argparse
+    ap = argparse.ArgumentParser(prog="mesh_cull")
+    sub = ap.add_subparsers(dest="command", required=True)
+    t = sub.add_parser("tnt", help="eval_tnt/cull_mesh.py: keep what at least --min-views cameras see, write <ply>_cull.ply")
+    t.add_argument("--traj-path", type=str, required=True)
+    t.add_argument("--ply-path", type=str, required=True)
+    for k, val in TNT_INTRINSICS.items():
+        t.add_argument("--" + k, type=type(val), default=val)
+    t.add_argument("--min-views", type=int, default=20)
+    t.add_argument("--components", type=str, default=None, help="a mesh_components spec, e.g. largest:1")
+    a = ap.parse_args(argv)
+    comp = None
+    if a.components:
+        import mesh_components
+        comp = mesh_components.parse_spec(a.components)
+    mesher = TntMesher(a.height, a.width, a.fx, a.fy, a.cx, a.cy, 20.0, points_batch_size=5e5, components=comp)
+    mesher.min_views = a.min_views
+    mesher(a.ply_path, get_traj(a.traj_path))
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main(sys.argv[1:]))

@@ -5,7 +5,9 @@
  * (a) disk dilation of every view's object mask, (b) projection of every vertex into every view and the test against the dilated
  * masks, (c) compaction of the mesh to the kept vertices and the faces between them.  And what that script and
  * eval_tnt/cull_mesh.py:186-201 leave disabled for want of a split() that scales: (d) the connected components of the mesh, their
- * sizes, and the masks that drop the small ones (csrc/mesh_components.hip).
+ * sizes, and the masks that drop the small ones (csrc/mesh_components.hip).  And what eval_tnt/cull_mesh.py asks of
+ * pyrender and of its point_masks: (e) a depth image of the mesh per camera, (f) the number of views that see a vertex in front of it
+ * (csrc/mesh_raster.hip).
  *
  * Conventions as in gof_hip.h: extern "C", device pointers, caller-owned workspace with a *_bytes query whose contents do not
  * matter on entry, launches on `stream`, 0 = ok, negative = GOF_E_* with text in gof_last_error().  Every operation that decides
@@ -107,6 +109,76 @@ int gof_mesh_component_mask(int64_t num_faces, const int32_t* face_comp, int64_t
  * Indices outside [0, NV) mark nothing (gof_mesh_compact refuses them).  No workspace, no wait. */
 int gof_mesh_mark_referenced(int64_t num_vertices, int64_t num_faces, const int32_t* faces, const uint8_t* face_keep,
                              uint8_t* vert_keep, void* stream);
+
+/* ---- (e) depth rasteriser, (f) visibility count (csrc/mesh_raster.hip) ----------------------------------------------
+ * What eval_tnt/cull_mesh.py asks of pyrender (a depth image of the mesh per camera, :17-66) and of Mesher.point_masks (:117-175).
+ * This part of the header is version 3 of the mesh ABI: gof_mesh_raster_abi_version() = 3.  gof_mesh_abi_version() keeps answering 2:
+ * (a)-(d) are unchanged and their callers compare that number.
+ *
+ * One record per view, in device memory: w2c = rows 0..2 of world-to-camera (row-major 3 x 4, fp64; OpenCV convention: +x right, +y
+ * down, +z forward), the intrinsics and the depth range in fp64, the image size.  Image v of a call lies at depth + v * view_stride
+ * (in elements; W * H <= view_stride for every record).  1 <= W, H <= 16384, znear > 0, zfar > znear, else GOF_E_INVALID; so is a
+ * face index outside [0, NV).  Both are checked by a launch of their own before any output is written; that check waits for the
+ * stream once.  3 * NF < 2^31.
+ *
+ * (e) gof_mesh_render_depth: vertices [NV,3] float32 (widened to fp64), faces [NF,3] int32 -> depth: per view H x W float32, row 0
+ * at the top, pixel (i, j) = column i of row j with its centre at (i + 0.5, j + 0.5); both orientations of a face are drawn.  Per face
+ * and view, every operation IEEE fp64 in this order, nothing contracted:
+ *   camera coordinates of a vertex: x = ((w2c[0] vx + w2c[1] vy) + w2c[2] vz) + w2c[3], y and z from rows 1 and 2; a face with a
+ *   non-finite vertex coordinate or camera coordinate is skipped;
+ *   Sutherland-Hodgman against z >= znear, walking the edges v0v1, v1v2, v2v0: an inside vertex is emitted, then, if the edge crosses,
+ *   the point p = a + t (b - a) with t = (znear - za) / (zb - za), a the INSIDE endpoint and b the outside one, for x and y, and
+ *   z = znear itself;
+ *   projection of every vertex of that polygon: sx = fx (x / z) + cx, sy = fy (y / z) + cy, w = 1 / z; a non-finite sx or sy skips
+ *   the face;
+ *   the same clip, with the same rule for a and b and all of sx, sy, w interpolated by t except the clipped coordinate, which is the
+ *   bound itself, against sx >= -G, sx <= W + G, sy >= -G, sy <= H + G in this order, G = 4096 pixels;
+ *   the polygon q0 .. q(n-1) is fanned: (q0, qk, qk+1), k = 1 .. n - 2.  Per triangle (A, B, C): X = (int) rint(sx * 256), Y likewise;
+ *   area = (Bx - Ax)(Cy - Ay) - (By - Ay)(Cx - Ax) in integers; 0: skipped; negative: B and C change places and area = -area.
+ *   Pixel (i, j), P = (256 i + 128, 256 j + 128): e0 = (Cx - Bx)(Py - By) - (Cy - By)(Px - Bx), e1 the same from C to A, e2 from A to
+ *   B; covered iff each ek > 0 or ek = 0 and its edge (dx, dy) = end - start has dy < 0 or (dy = 0 and dx > 0) (top-left rule);
+ *   z = (double) area / (((double) e0 wA + (double) e1 wB) + (double) e2 wC); kept iff z > 0 and z <= zfar; d = (float) z.
+ * A pixel holds the minimum of its d (an unsigned integer minimum over the floats' bit patterns: no floating-point atomics, the same
+ * bits whatever the order of the faces and on every run), 0.0f where nothing is kept.  All |X|, |Y| < 2^23, so an edge function is
+ * below 2^49 and exact in int64 and in fp64.
+ * stats (host, may be NULL; 8 words): [0] fan triangles with a non-empty pixel box, [1] of them walked through the list, [2] refused by
+ * a full list and drawn by their own thread, [3] atomics issued, [4] pixels covered and in range.  Collecting them costs time. */
+typedef struct GofRasterView {
+    double w2c[12];
+    double fx, fy, cx, cy, znear, zfar;
+    int32_t W, H;
+} GofRasterView;
+
+int gof_mesh_raster_abi_version(void); /* 3 */
+/* for tests: out[0] the largest side, in pixels, of a triangle's box of pixel centres that its own thread draws (larger: the list),
+ * out[1], out[2] width and height of the tile a wave walks the list's triangles with, out[3] G, out[4] the largest W or H, out[5] the
+ * views per batch of gof_mesh_visibility with batch = 0, out[6] list entries the workspace holds besides NF / 8, out[7] workgroups
+ * that share one list entry */
+void gof_mesh_raster_tiling(int64_t* out);
+size_t gof_mesh_render_depth_ws_bytes(int64_t num_faces);
+int gof_mesh_render_depth(int64_t num_vertices, const float* vertices, int64_t num_faces, const int32_t* faces, int32_t num_views,
+                          const GofRasterView* views, int64_t view_stride, float* depth, int64_t* stats, void* ws, size_t ws_bytes,
+                          void* stream);
+
+/* (f) count [NV] int32 += the number of views that see the vertex in front of their depth image (Mesher.point_masks in fp64).  Per
+ * vertex and view: x, y, Z as in (e); X = fx x + cx Z, Y = fy y + cy Z; z = Z + 1e-8; u = X / z, v = Y / z;
+ *   in_frustum = u >= 0 && u <= W - 1 && v >= 0 && v <= H - 1 && z > 0 (false for NaN); only then the image is read:
+ *   x0 = floor(u), x1 = min(x0 + 1, W - 1), tx = u - x0, y likewise (grid_sample, bilinear, align_corners = True, border padding: the
+ *   texel index is the coordinate); with dyx the texels widened to fp64:
+ *   ds = ((d00 ((1 - tx)(1 - ty)) + d01 (tx (1 - ty))) + d10 ((1 - tx) ty)) + d11 (tx ty);
+ *   front = ds > 0 ? z < ds + eps : true;  the view counts iff in_frustum && front.
+ * The workspace is gof_mesh_render_depth_ws_bytes(0) bytes. */
+int gof_mesh_visible_count(int64_t num_vertices, const float* vertices, int32_t num_views, const GofRasterView* views,
+                           int64_t view_stride, const float* depth, double eps, int32_t* count, void* ws, size_t ws_bytes,
+                           void* stream);
+
+/* The two together: `batch` views (0: out[5] of the tiling query; at most 4096) are rendered into the workspace and counted, batch
+ * after batch; the depth images of all views never exist at once.  count [NV] int32 (written, not added to), keep [NV] uint8 =
+ * count >= min_views (min_views <= 0 keeps everything).  stats as in (e), summed over the batches. */
+size_t gof_mesh_visibility_ws_bytes(int64_t num_faces, int64_t view_stride, int32_t batch);
+int gof_mesh_visibility(int64_t num_vertices, const float* vertices, int64_t num_faces, const int32_t* faces, int32_t num_views,
+                        const GofRasterView* views, int64_t view_stride, int32_t batch, double eps, int32_t min_views, int32_t* count,
+                        uint8_t* keep, int64_t* stats, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
