@@ -109,6 +109,11 @@ What it does, in this order (nothing in the reference checkout is edited):
      and its intrinsics run as they are.  `import pyrender` resolves to the stand-in of shims/ where pyrender is not installed, open3d,
      trimesh and cv2 to theirs (2., 10., 13.).  The mesh that is culled is the file the script is given (its own
      extract_depth_from_mesh loads a file of its author's, :28).  GOF_TNT_CULL_TORCH=1 leaves the script alone.
+ 19. mesh_viewer.py PATH asks Open3D for compute_vertex_normals and an OpenGL window (:48-71); no window can open on a machine without
+     a display, so the headless stand-in runs instead: mesh_render's command line (csrc/mesh_render.hip, DESIGN.md 3.20: area-weighted
+     vertex normals, a face buffer beside the z-buffer, a resolve pass) with `PATH --turntable 8 --mode shaded --out PATH_views/`, which
+     writes PATH_views/00000.png .. 00007.png through image_writer.  Open3D is not imported.  GOF_MESH_VIEWER_WINDOW=1 leaves the script
+     alone.
 """
 import importlib
 import os
@@ -654,11 +659,31 @@ def tnt_eval_rebinding(script):
     return {"main": _tnt_eval_main}
 
 
+def _mesh_viewer_main(argv):
+    import mesh_render
+    if len(argv) != 1:
+        print("Usage: mesh_viewer.py path_to_ply_file")
+        return 2
+    return mesh_render.main([argv[0], "--turntable", "8", "--mode", "shaded", "--out", argv[0] + "_views"])
+
+
+def mesh_viewer_rebinding(script):
+    """what replaces `script` as a whole for the mesh viewer (19.): {"main": mesh_render's command line over a turntable} for
+    mesh_viewer.py, unless GOF_MESH_VIEWER_WINDOW=1 asks for the script's own window"""
+    if os.path.basename(script) != "mesh_viewer.py" or os.environ.get("GOF_MESH_VIEWER_WINDOW", "0") == "1":
+        return {}
+    return {"main": _mesh_viewer_main}
+
+
 def main():
     if len(sys.argv) < 2:
         print(__doc__)
         sys.exit(2)
     script = os.path.abspath(sys.argv[1])
+    viewer = mesh_viewer_rebinding(script)
+    if viewer:
+        sys.path.insert(0, PKG)
+        sys.exit(viewer["main"](sys.argv[2:]))
     tnt = tnt_eval_rebinding(script)
     if tnt:
         sys.path.insert(0, PKG)

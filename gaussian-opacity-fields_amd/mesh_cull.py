@@ -351,6 +351,13 @@ class DeviceMesh:
         self.remove_unreferenced_vertices()
         return count
 
+    def compute_vertex_normals(self):
+        """Open3D's name (mesh_viewer.py:48): area-weighted vertex normals (mesh_render.vertex_normals) into the
+        normals that export() writes -> self"""
+        import mesh_render
+        self._n = mesh_render.vertex_normals(self)
+        return self
+
     def export(self, path):
         """binary little-endian PLY: float x y z [nx ny nz] [uchar red green blue], `list uchar int` faces"""
         v = self._v.cpu().numpy()

@@ -7,7 +7,8 @@
  * eval_tnt/cull_mesh.py:186-201 leave disabled for want of a split() that scales: (d) the connected components of the mesh, their
  * sizes, and the masks that drop the small ones (csrc/mesh_components.hip).  And what eval_tnt/cull_mesh.py asks of
  * pyrender and of its point_masks: (e) a depth image of the mesh per camera, (f) the number of views that see a vertex in front of it
- * (csrc/mesh_raster.hip).
+ * (csrc/mesh_raster.hip).  And what mesh_viewer.py asks of Open3D and a window: (g) vertex normals, a face buffer and the
+ * images resolved from it (csrc/mesh_render.hip).
  *
  * Conventions as in gof_hip.h: extern "C", device pointers, caller-owned workspace with a *_bytes query whose contents do not
  * matter on entry, launches on `stream`, 0 = ok, negative = GOF_E_* with text in gof_last_error().  Every operation that decides
@@ -179,6 +180,70 @@ size_t gof_mesh_visibility_ws_bytes(int64_t num_faces, int64_t view_stride, int3
 int gof_mesh_visibility(int64_t num_vertices, const float* vertices, int64_t num_faces, const int32_t* faces, int32_t num_views,
                         const GofRasterView* views, int64_t view_stride, int32_t batch, double eps, int32_t min_views, int32_t* count,
                         uint8_t* keep, int64_t* stats, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- (g) pictures of the surface: vertex normals, face buffer, resolve (csrc/mesh_render.hip) ------------------------
+ * What the reference's mesh_viewer.py asks of Open3D (compute_vertex_normals, then an OpenGL window).  Version 4 of the mesh ABI:
+ * gof_mesh_render_abi_version() = 4; the three older numbers keep their values.  Every output is a pure function of the input, in
+ * integers and IEEE fp64 without contraction in the written order; with
+ *   cross(a, b) = (ay bz - az by, az bx - ax bz, ax by - ay bx),  dot(u, v) = (ux vx + uy vy) + uz vz,
+ *   unit(n): len = sqrt((nx nx + ny ny) + nz nz); n / len per component if len is finite and > 0, else (0, 0, 1).
+ * Refused input (a face index outside [0, NV), a bad view record, a bad mode, ...) is GOF_E_INVALID with no output written; the
+ * indices and records are checked by a launch of their own, which waits for the stream once.  3 * NF < 2^31.
+ *
+ * (g1) normals.  vertices [NV,3] float32 widened to fp64.  Face vector Nf = cross(v1 - v0, v2 - v0), not normalised (area weights).
+ * gof_mesh_face_normals: out [NF,3] float32 = (float) unit(Nf).  gof_mesh_vertex_normals: out [NV,3] float32 = (float) unit(S), S = the
+ * sum of Nf over the vertex's incident corners in ascending 3 * face + corner order, one addition per corner, starting from 0 (a
+ * vertex without a face, or with S = 0 or not finite: (0, 0, 1)).  No floating-point atomics: the corners are counted per vertex,
+ * the counts scanned, the (vertex, corner) pairs sorted stably by vertex, and one lane per vertex walks its segment. */
+int gof_mesh_render_abi_version(void); /* 4 */
+size_t gof_mesh_vertex_normals_ws_bytes(int64_t num_vertices, int64_t num_faces);
+int gof_mesh_vertex_normals(int64_t num_vertices, const float* vertices, int64_t num_faces, const int32_t* faces, float* normals,
+                            void* ws, size_t ws_bytes, void* stream);
+size_t gof_mesh_face_normals_ws_bytes(void);
+int gof_mesh_face_normals(int64_t num_vertices, const float* vertices, int64_t num_faces, const int32_t* faces, float* normals,
+                          void* ws, size_t ws_bytes, void* stream);
+
+/* (g2) face buffer.  The inputs of gof_mesh_render_depth; geometry and coverage are those of (e).  A pixel keeps the minimum of the
+ * 64-bit word (bits(d) << 32) | face over everything that covers it (one unsigned 64-bit atomic minimum): the smallest depth and,
+ * among equal depth bits, the smallest face index.  depth: per view H x W float32, bit-equal to (e)'s; face: per view H x W int32, -1
+ * where nothing is seen; image v of both at + v * view_stride elements.  The workspace holds 8 bytes per pixel of the call
+ * (num_views * view_stride words) besides (e)'s; the tiling query of (e) describes this entry as well.  stats as in (e).  The size
+ * query answers 0 for num_views outside [0, 65535] or view_stride outside [0, 16384^2]. */
+size_t gof_mesh_render_faces_ws_bytes(int64_t num_faces, int32_t num_views, int64_t view_stride);
+int gof_mesh_render_faces(int64_t num_vertices, const float* vertices, int64_t num_faces, const int32_t* faces, int32_t num_views,
+                          const GofRasterView* views, int64_t view_stride, float* depth, int32_t* face, int64_t* stats, void* ws,
+                          size_t ws_bytes, void* stream);
+
+/* (g3) resolve: one lane per pixel reads `face` (as (g2) wrote it; a value outside [0, NF) is background).  For pixel (i, j) with
+ * face f: a, b, c = the camera coordinates of the face's ORIGINAL three vertices as in (e); d = (((i + 0.5) - cx) / fx,
+ * ((j + 0.5) - cy) / fy, 1);  m0 = dot(d, cross(b, c)), m1 = dot(d, cross(c, a)), m2 = dot(d, cross(a, b));  s = (m0 + m1) + m2,
+ * lk = mk / s;  each lk that is NaN or < 0 becomes 0, each > 1 becomes 1;  t = (l0 + l1) + l2;  lk /= t if t > 0, else all three are
+ * 1/3: the perspective-correct barycentric coordinates of the ray through the pixel centre (a clipped face gives what an unclipped
+ * one gives).  sum3(q) = (l0 q0 + l1 q1) + l2 q2 per component.
+ * image: per view three planes of view_stride float32 (plane c of view v at (3 v + c) * view_stride), bary (may be NULL) likewise =
+ * (float) lk.  Background pixels get (float) background[c] and a bary of 0.  Modes:
+ *   NORMAL_WORLD   n = unit(sum3(N)) with N the vertex normals widened (normals [NV,3] float32); with GOF_SHADE_FLAT n = unit(Nf) of
+ *                  (g1) instead and `normals` is not read;  out = (float)((n + 1) / 2).
+ *   NORMAL_CAMERA  nc = ((w2c[4r] nx + w2c[4r+1] ny) + w2c[4r+2] nz), r = 0, 1, 2;  out = (float)((nc + 1) / 2).
+ *   COLOR          out = (float)(sum3(C) / 255), C the vertex colours (colors [NV,4] uint8: red green blue and a pad byte).
+ *   SHADED         p = sum3 of (a, b, c); v = unit(-p); l = |dot(nc, v)| (a two-sided headlight); out = (float)(base (amb + (1 - amb) l));
+ *                  base = sum3(C) / 255 with GOF_SHADE_VERTEX_BASE, else the record's base.
+ * GOF_E_INVALID besides the above: a mode above the last, flags beyond the two, an ambient that is not finite, colours needed and
+ * NULL, normals needed and NULL.  The workspace is a few words. */
+#define GOF_SHADE_NORMAL_WORLD 0
+#define GOF_SHADE_NORMAL_CAMERA 1
+#define GOF_SHADE_COLOR 2
+#define GOF_SHADE_SHADED 3
+#define GOF_SHADE_FLAT 1
+#define GOF_SHADE_VERTEX_BASE 2
+typedef struct GofShadeParams {
+    int32_t mode, flags;
+    double base[3], background[3], ambient;
+} GofShadeParams;
+size_t gof_mesh_shade_ws_bytes(void);
+int gof_mesh_shade(int64_t num_vertices, const float* vertices, int64_t num_faces, const int32_t* faces, const float* normals,
+                   const uint8_t* colors, int32_t num_views, const GofRasterView* views, int64_t view_stride, const int32_t* face,
+                   const GofShadeParams* params, float* image, float* bary, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
