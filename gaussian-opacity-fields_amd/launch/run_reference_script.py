@@ -102,6 +102,9 @@ What it does, in this order (nothing in the reference checkout is edited):
      DESIGN.md 3.18).  The replacements of 9. and of extract_mesh_tsdf.py's `tsdf_fusion` first write the file they always wrote, byte for
      byte; then that file is read back, reduced to the selected components and written next to it as mesh_binary_search_7_clean.ply /
      tsdf_clean.ply.  A malformed spec is an error before the script starts.  Unset: nothing differs.
+     Likewise GOF_MESH_SIMPLIFY=<spec> (`grid:1024`, `target_vertices:2000000`, `cell:0.01,dedupe:0`; the keyword arguments of
+     DeviceMesh.simplify: mesh_simplify.py, csrc/mesh_simplify.hip) writes mesh_binary_search_7_simplified.ply /
+     tsdf_simplified.ply next to the file, from the cleaned mesh where GOF_MESH_COMPONENTS is set as well, else from the file itself.
  18. eval_tnt/cull_mesh.py asks pyrender (OpenGL over EGL) for a depth image of the mesh per camera and torch for the views that see each
      vertex in front of it: for a script that defines both `Mesher` and `extract_depth_from_mesh` the two names become
      mesh_cull.TntMesher and mesh_cull.render_depth (csrc/mesh_raster.hip, DESIGN.md 3.19: a triangle rasteriser with a z-buffer and the
@@ -619,6 +622,43 @@ def mesh_components_rebinding(rebind):
             if name in rebind}
 
 
+def mesh_simplify_spec():
+    """GOF_MESH_SIMPLIFY=<spec> -> the keyword arguments of DeviceMesh.simplify, None where it is unset or empty; a malformed spec
+    raises ValueError (main() asks before the script starts)"""
+    spec = os.environ.get("GOF_MESH_SIMPLIFY", "")
+    if not spec.strip():
+        return None
+    import mesh_simplify
+    return mesh_simplify.parse_spec(spec)
+
+
+SIMPLIFIED_MESH_FILES = {"mesh_binary_search_7.ply": "mesh_binary_search_7_simplified.ply", "tsdf.ply": "tsdf_simplified.ply"}
+
+
+def _with_simplified_mesh(fn, subdir, written, clean, how):
+    def run(model_path, name, iteration, *args, **kwargs):
+        out = fn(model_path, name, iteration, *args, **kwargs)       # (writes its file, and with GOF_MESH_COMPONENTS the cleaned one, first)
+        import mesh_simplify
+        folder = os.path.join(model_path, name, "ours_{}".format(iteration), subdir)
+        src = os.path.join(folder, clean if mesh_components_spec() is not None else written)
+        dst = os.path.join(folder, SIMPLIFIED_MESH_FILES[written])
+        st = mesh_simplify.simplify_file(src, dst, **how)
+        print("mesh simplify: %d -> %d faces (cell %.9g) -> %s" % (st["faces_before"], st["faces_after"], st["cell"], dst))
+        return out
+    return run
+
+
+def mesh_simplify_rebinding(rebind):
+    """the entries of `rebind` that write a mesh (after mesh_components_rebinding has wrapped them), wrapped so that the simplified mesh
+    is written next to theirs -- only where GOF_MESH_SIMPLIFY is set (17.); the cleaned mesh is the input where GOF_MESH_COMPONENTS is
+    set as well"""
+    how = mesh_simplify_spec()
+    if how is None:
+        return {}
+    return {name: _with_simplified_mesh(rebind[name], subdir, written, clean, how) for name, subdir, written, clean in CLEAN_MESH_FILES
+            if name in rebind}
+
+
 def _tnt_mesher(*args, **kwargs):
     import mesh_cull
     return mesh_cull.TntMesher(*args, **kwargs)
@@ -750,6 +790,7 @@ def main():
     rebind.update(png_reader_rebinding(script))
     rebind.update(tnt_cull_rebinding(script))
     rebind.update(mesh_components_rebinding(rebind))
+    rebind.update(mesh_simplify_rebinding(rebind))
     try:
         run_script(script, rebind)
     except BaseException:

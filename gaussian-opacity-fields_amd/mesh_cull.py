@@ -340,6 +340,32 @@ class DeviceMesh:
                                          "comp_area": comps.area.tolist()}
         return kept, len(keep) - kept
 
+    # ---- simplification (mesh_simplify.py)
+    def simplify(self, cell=None, grid=None, target_vertices=None, dedupe=True, origin=None):
+        """In place: uniform vertex clustering with a quadric-error representative -> the statistics.  Exactly one of cell (the cell
+        size h), grid (h = the largest extent of the bounding box / grid) and target_vertices (the smallest probed h with at most that
+        many clusters: at most 24 count-only probes).  The grid's origin is the smallest coordinate per axis unless `origin` names one.  Every vertex of a cell
+        becomes one vertex (the regularised quadric minimiser, or the cell's mean; a cell of one vertex keeps it bit for bit), colours their integer mean; a face with two
+        corners in one cell goes, with dedupe also all but the first face of an unordered triple of cells; kept faces keep their order
+        and orientation; cells no kept face refers to go; normals, if the mesh had them, are computed anew."""
+        import mesh_simplify
+        nv, nf = int(self._v.size(0)), int(self._f.size(0))
+        h, probes = mesh_simplify.choose_cell(self._v, cell, grid, target_vertices, origin)
+        out = mesh_simplify.simplify(self._v, self._f, self._c, cell=h, dedupe=dedupe, origin=origin)
+        had_normals = self._n is not None
+        self._v, self._c, self._n = out["cluster_vertices"], out["cluster_colors"], None
+        with _device_of(self._v):
+            self._f = _gather(_compact_rows(out["face_keep"]), out["cluster_faces"]) if nf else out["cluster_faces"]
+        self.remove_unreferenced_vertices()
+        if had_normals:
+            self.compute_vertex_normals()
+        stats = {"vertices_before": nv, "faces_before": nf, "vertices_after": int(self._v.size(0)), "faces_after": int(self._f.size(0)),
+                 "clusters": out["clusters"], "used_mean": out["used_mean_count"], "dropped_degenerate": out["dropped_degenerate"],
+                 "dropped_duplicate": out["dropped_duplicate"], "cell": h, "origin": out["origin"], "dedupe": bool(dedupe),
+                 "probes": [[p, n] for p, n in probes]}
+        mesh_simplify._last["mesh"] = stats
+        return dict(stats)
+
     def cull_by_visibility(self, c2w_list, H, W, fx, fy, cx, cy, zfar=20.0, eps=0.005, min_views=20, znear=0.01, convention="opengl", batch=0):
         """eval_tnt/cull_mesh.py:220-249 in place: a depth image of this mesh per camera, the views that see each vertex in front of it,
         then update_faces(every vertex seen by at least min_views) and remove_unreferenced_vertices -> the per-vertex counts (before

@@ -8,7 +8,8 @@
  * sizes, and the masks that drop the small ones (csrc/mesh_components.hip).  And what eval_tnt/cull_mesh.py asks of
  * pyrender and of its point_masks: (e) a depth image of the mesh per camera, (f) the number of views that see a vertex in front of it
  * (csrc/mesh_raster.hip).  And what mesh_viewer.py asks of Open3D and a window: (g) vertex normals, a face buffer and the
- * images resolved from it (csrc/mesh_render.hip).
+ * images resolved from it (csrc/mesh_render.hip).  And what the reference's README leaves to MeshLab: (h) a mesh with fewer
+ * faces, by vertex clustering with a quadric-error representative (csrc/mesh_simplify.hip).
  *
  * Conventions as in gof_hip.h: extern "C", device pointers, caller-owned workspace with a *_bytes query whose contents do not
  * matter on entry, launches on `stream`, 0 = ok, negative = GOF_E_* with text in gof_last_error().  Every operation that decides
@@ -244,6 +245,60 @@ size_t gof_mesh_shade_ws_bytes(void);
 int gof_mesh_shade(int64_t num_vertices, const float* vertices, int64_t num_faces, const int32_t* faces, const float* normals,
                    const uint8_t* colors, int32_t num_views, const GofRasterView* views, int64_t view_stride, const int32_t* face,
                    const GofShadeParams* params, float* image, float* bary, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- (h) simplification: uniform vertex clustering with a quadric-error representative (csrc/mesh_simplify.hip) ----
+ * What every user of fusion/mesh_binary_search_7.ply does first in some other tool.  Version 5 of the mesh ABI:
+ * gof_mesh_simplify_abi_version() = 5; the four older numbers keep their values.  vertices [NV,3] fp64, faces [NF,3] int32 with indices
+ * in [0, NV), 3 * NF < 2^31, origin: 3 doubles ON THE HOST, h the cell size.  Refused with GOF_E_INVALID and nothing written (the
+ * inputs are checked by a launch of their own, which waits for the stream once): an index outside [0, NV), a cluster number outside
+ * [0, NC), a vertex / origin / h that is not finite, h <= 0, a cell coordinate outside [0, 2^21).  Every operation below is an integer
+ * operation or IEEE fp64 without contraction in the written order; no floating-point atomics; the bits depend neither on the run nor
+ * on the workspace.
+ *
+ * gof_mesh_cluster.  Cell of a vertex: i_a = floor((x_a - o_a) / h) per axis; key = ix 2^42 + iy 2^21 + iz.  A cluster is a cell with a
+ * vertex; the clusters are numbered 0 .. NC-1 in the order of their smallest vertex index.  vertex_cluster [NV] int32 (NULL: the
+ * clusters are only counted), *num_clusters (host) = NC. */
+int gof_mesh_simplify_abi_version(void); /* 5 */
+/* the sizes at which this unit changes its path, for tests: out[0] items per block of the radix sort, out[1] items per tile of the
+ * scan, out[2] positions per tile and out[3] per block of the sums */
+void gof_mesh_simplify_tiling(int64_t* out);
+size_t gof_mesh_cluster_ws_bytes(int64_t num_vertices);
+int gof_mesh_cluster(int64_t num_vertices, const double* vertices, const double* origin, double h, int32_t* vertex_cluster,
+                     int64_t* num_clusters, void* ws, size_t ws_bytes, void* stream);
+
+/* gof_mesh_cluster_solve.  Per cluster (vertex_cluster [NV] as above, or any numbering with values in [0, NC)): its cell is that of
+ * its smallest vertex, centre_a = o_a + (i_a + 0.5) h.  With q = p - centre per component:
+ *   mean m = (sum of its vertices' q) / n;  colour channel = (2 S + n) / (2 n) in integers, S the sum of the channel, pad byte 0;
+ *   quadric: over the corners e = 3 f + k whose vertex lies in the cluster, with q0, q1, q2 the face's three vertices:
+ *     e1 = q1 - q0, e2 = q2 - q0;  n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x);  L = sqrt((nx nx + ny ny) + nz nz);
+ *     L == 0: ten zeros; else w = 0.5 / L, d = -((nx q0x + ny q0y) + nz q0z), wn = w n per component, wd = w d and
+ *     A = (wnx nx, wnx ny, wnx nz, wny ny, wny nz, wnz nz), b = (wd nx, wd ny, wd nz), c = wd d.
+ *   Both sums run over the items stably sorted by cluster (ascending vertex index, ascending e) in the order of (d): inside a tile of
+ *   256 sorted positions from left to right starting from the first, the tile sums inside a block of 65536 positions from left to
+ *   right, the block sums from left to right.
+ *   t = (Axx + Ayy) + Azz.  t == 0: y = m.  Else lambda = t * 2^-10, M = A + lambda I, r = lambda m - b and
+ *     l00 = sqrt(M00), l10 = M01 / l00, l20 = M02 / l00, l11 = sqrt(M11 - l10 l10), l21 = (M12 - l20 l10) / l11,
+ *     l22 = sqrt((M22 - l20 l20) - l21 l21);  z0 = r0 / l00, z1 = (r1 - l10 z0) / l11, z2 = ((r2 - l20 z0) - l21 z1) / l22;
+ *     y2 = z2 / l22, y1 = (z1 - l21 y2) / l11, y0 = ((z0 - l10 y1) - l20 y2) / l00;  unless every |y_a| <= 0.5 h: y = m.
+ *   A cluster of ONE vertex skips the solve: y = m and its output is that vertex's own three doubles, bit for bit (every plane of its
+ *   quadric passes through the vertex, so the vertex is the minimiser; centre + (p - centre) need not reproduce p).
+ * out_vertices [NC,3] fp64 = centre + y (one vertex: the vertex); out_colors [NC,4] uint8 (NULL iff colors is NULL); used_mean [NC] uint8 = y is m;
+ * *used_mean_count (host, may be NULL) = their number.  Waits for the stream once more at its end (the sorts' status; GOF_E_DEVICE if one gave up).  A cluster without a vertex (a caller's numbering)
+ * gets the origin-independent position 0 + 0 and used_mean = 1. */
+size_t gof_mesh_cluster_solve_ws_bytes(int64_t num_vertices, int64_t num_faces, int64_t num_clusters);
+int gof_mesh_cluster_solve(int64_t num_vertices, int64_t num_faces, const double* vertices, const int32_t* faces, const uint8_t* colors,
+                           const int32_t* vertex_cluster, int64_t num_clusters, const double* origin, double h, double* out_vertices,
+                           uint8_t* out_colors, uint8_t* used_mean, int64_t* used_mean_count, void* ws, size_t ws_bytes, void* stream);
+
+/* gof_mesh_cluster_faces.  out_faces [NF,3] int32 = vertex_cluster of every index, in the face's order.  face_keep [NF] uint8: 0 for a
+ * face whose three clusters are not pairwise distinct; with dedupe != 0 also 0 for a face whose unordered triple of clusters is that of
+ * a kept face with a smaller index (the triples sorted to a < b < c go through three stable sorts by c, b, a; an entry that equals its
+ * predecessor is dropped); 1 otherwise.  counts (host, may be NULL): [0] faces dropped as degenerate,
+ * [1] as duplicates.  Waits for the stream once more at its end (the sorts' status; GOF_E_DEVICE if one gave up). */
+size_t gof_mesh_cluster_faces_ws_bytes(int64_t num_faces);
+int gof_mesh_cluster_faces(int64_t num_vertices, int64_t num_faces, const int32_t* faces, const int32_t* vertex_cluster,
+                           int64_t num_clusters, int32_t dedupe, int32_t* out_faces, uint8_t* face_keep, int64_t* counts, void* ws,
+                           size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
