@@ -10,7 +10,10 @@ size_t scan_tmp_words(size_t n);
 hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
                            const uint32_t** total_dev_out, hipStream_t stream);
 
-// ---- stable sort of (key, value) pairs on key bits [0, end_bit); tmp: rs_tmp_words(n) u32; the result aliases a* or b* ----------------
+// ---- stable sort of (key, value) pairs by WHOLE 8-bit digits; tmp: rs_tmp_words(n) u32; the result aliases a* or b* -------------------
+// The order is by key bits [0, 8 * radix_passes(end_bit)), not [0, end_bit): a pass takes (key >> shift) & 0xFF, so where end_bit is no
+// multiple of 8 the bits from end_bit up to the next multiple take part.  A caller's keys are clear there (every caller derives end_bit
+// from the largest key) or it wants them sorted.  The result lies in a* after an even number of passes (and for n == 0), else in b*.
 size_t rs_tmp_words(size_t n);
 hipError_t radix_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, size_t n, int end_bit,
                                 uint32_t* tmp, uint32_t** keys_res, uint32_t** vals_res, hipStream_t stream, const uint32_t* n_dev = nullptr);

@@ -171,13 +171,23 @@ size_t scan_tmp_words(size_t n) { return (n + 256 * SCAN_ITEMS_SMALL - 1) / (256
 // out = scan(in[idx]) if idx != nullptr else scan(in).  tmp: scan_tmp_words(n) u32.  The grand total is left in
 // tmp[nblocks] (device); total_dev_out (optional) receives its address.
 // total_host (nullable): a DEVICE-VISIBLE address of host memory (hipHostGetDevicePointer) that receives the grand total as well.
+// The form a scan of n words runs in -- the one place that decides it: small tiles while the two-launch form still holds with them
+// (<= SCAN_DIRECT_MAX workgroups of 1024 words), big tiles above; the two-launch form up to SCAN_DIRECT_MAX workgroups of either.
+struct ScanPlan { uint32_t tile, nb; bool direct; };
+static ScanPlan scan_plan(size_t n)
+{
+    ScanPlan p;
+    p.tile = 256u * (uint32_t)(n <= (size_t)SCAN_DIRECT_MAX * 256 * SCAN_ITEMS_SMALL ? SCAN_ITEMS_SMALL : SCAN_ITEMS_BIG);
+    p.nb = (uint32_t)((n + p.tile - 1) / p.tile);
+    p.direct = p.nb <= SCAN_DIRECT_MAX;         // few workgroups: each adds up its predecessors' sums itself, two launches
+    return p;
+}
 template <int ITEMS>
 static hipError_t device_scan_t(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
                                 const uint32_t** total_dev_out, hipStream_t stream, uint32_t* total_host,
-                                const uint32_t* hist_items_dev, uint32_t capacity)
+                                const uint32_t* hist_items_dev, uint32_t capacity, const ScanPlan& plan)
 {
-    constexpr size_t BLOCK = 256 * ITEMS;
-    const uint32_t nb = (uint32_t)((n + BLOCK - 1) / BLOCK);
+    const uint32_t nb = plan.nb;
     if (total_dev_out) *total_dev_out = tmp + nb;
     if (n == 0) {
         if (total_host) *total_host = 0;       // (host-mapped: a plain host store; nothing is queued for an empty input)
@@ -185,7 +195,7 @@ static hipError_t device_scan_t(const uint32_t* in, const uint32_t* idx, uint32_
     }
     if (idx) hipLaunchKernelGGL((scan_block_sums_gather<true, ITEMS>), dim3(nb), dim3(256), 0, stream, in, idx, (uint32_t)n, tmp);
     else hipLaunchKernelGGL((scan_block_sums<ITEMS>), dim3(nb), dim3(256), 0, stream, in, (uint32_t)n, tmp, hist_items_dev, capacity);
-    const bool direct = nb <= SCAN_DIRECT_MAX;         // few workgroups: each adds up its predecessors' sums itself, two launches
+    const bool direct = plan.direct;
     if (!direct) hipLaunchKernelGGL(scan_sums, dim3(1), dim3(256), 0, stream, tmp, nb, total_host);
 #define GOF_SCAN_APPLY(INC, GA)                                                                                                        \
     do { if (direct) hipLaunchKernelGGL((scan_apply<INC, GA, true, ITEMS>), dim3(nb), dim3(256), 0, stream, in, idx, (uint32_t)n, tmp, out, total_host, hist_items_dev, capacity);   \
@@ -199,10 +209,10 @@ static hipError_t device_scan_impl(const uint32_t* in, const uint32_t* idx, uint
                                    const uint32_t** total_dev_out, hipStream_t stream, uint32_t* total_host,
                                    const uint32_t* hist_items_dev, uint32_t capacity)
 {
-    // small tiles while the two-launch form still holds (<= SCAN_DIRECT_MAX workgroups of 1024 items)
-    if (n <= (size_t)SCAN_DIRECT_MAX * 256 * SCAN_ITEMS_SMALL)
-        return device_scan_t<SCAN_ITEMS_SMALL>(in, idx, out, n, inclusive, tmp, total_dev_out, stream, total_host, hist_items_dev, capacity);
-    return device_scan_t<SCAN_ITEMS_BIG>(in, idx, out, n, inclusive, tmp, total_dev_out, stream, total_host, hist_items_dev, capacity);
+    const ScanPlan plan = scan_plan(n);
+    if (plan.tile == 256u * SCAN_ITEMS_SMALL)
+        return device_scan_t<SCAN_ITEMS_SMALL>(in, idx, out, n, inclusive, tmp, total_dev_out, stream, total_host, hist_items_dev, capacity, plan);
+    return device_scan_t<SCAN_ITEMS_BIG>(in, idx, out, n, inclusive, tmp, total_dev_out, stream, total_host, hist_items_dev, capacity, plan);
 }
 hipError_t device_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, size_t n, bool inclusive, uint32_t* tmp,
                            const uint32_t** total_dev_out, hipStream_t stream)
@@ -539,7 +549,8 @@ size_t rs_tmp_words(size_t n)
     return onesweep > classic ? onesweep : classic;
 }
 
-// Stable sort of (key, value) pairs on key bits [0, end_bit), 8 bits per pass.  Buffers a* hold the input; the
+// Stable sort of (key, value) pairs, one whole 8-bit digit per pass: the order is by key bits [0, 8 * ceil(end_bit / 8)) -- bits between
+// end_bit and the next multiple of 8 take part (radix.h).  Buffers a* hold the input; the
 // result ends up in (*keys_res, *vals_res), which alias either a* or b*.  n_dev (nullable): the item count lives on the device
 // (sync-free forward); n is then the CAPACITY the launches are sized for and every kernel clamps to min(n, *n_dev).
 // zero_words_behind: that many u32 words right behind the sort's scratch (tmp + rs_tmp_words(n)) are cleared as well -- by the memset the
@@ -666,4 +677,110 @@ hipError_t sort_keys63(const u64* keys, size_t n, const Sort63Ws& w, uint32_t** 
     return radix_sort_pairs_u32(w.hi[0], idx1, w.hi[1], idx_other, n, 31, w.tmp, &hi2, order, stream, nullptr);
 }
 
+// the workspace of gof_debug_sort_keys63: the six buffers and the sort's scratch, carved the way the units carve them
+static size_t debug_sort63_layout(void* base, size_t n, Sort63Ws* out)
+{
+    Carver c{ static_cast<char*>(base), 0 };
+    Sort63Ws w{};
+    sort63_carve(c, n, w);
+    w.tmp = c.take<uint32_t>(rs_tmp_words(n));
+    if (out) *out = w;
+    return c.total();
+}
+
 } // namespace gof
+
+// ---------------------------------------------------------------------------------------------------
+// Test support (include/gof_hip.h, the debug family): the functions above on buffers the caller chooses.  Nothing is reimplemented here:
+// argument checks, one call of the primitive, and copies of what it left (grand total, error word, order).
+// ---------------------------------------------------------------------------------------------------
+using namespace gof;
+
+extern "C" size_t gof_debug_prim_ws_bytes(int kind, int64_t n, size_t zero_words_behind)
+{
+    if (bad_count(n)) return 0;
+    if (kind == GOF_DEBUG_PRIM_SCAN) return scan_tmp_words((size_t)n) * sizeof(uint32_t);
+    if (kind == GOF_DEBUG_PRIM_SORT) return (rs_tmp_words((size_t)n) + zero_words_behind) * sizeof(uint32_t);
+    if (kind == GOF_DEBUG_PRIM_SORT63) return debug_sort63_layout(nullptr, (size_t)n, nullptr);
+    return 0;
+}
+
+extern "C" int gof_debug_prim_constants(int64_t n, int end_bit, uint32_t* block_items_host, int32_t* passes_host, size_t* zero_words_host,
+                                        int32_t* classic_hist_host)
+{
+    if (bad_count(n) || end_bit < 1 || end_bit > 32) { set_error("prim constants: n = %lld in [0, 2^31), end_bit = %d in 1..32", (long long)n, end_bit); return GOF_E_INVALID; }
+    uint32_t probe = 0;      // (radix_classic_hist only offsets the pointer it is given)
+    if (block_items_host) *block_items_host = rs_block_items();
+    if (passes_host) *passes_host = radix_passes(end_bit);
+    if (zero_words_host) *zero_words_host = radix_zero_words((size_t)n, end_bit);
+    if (classic_hist_host) *classic_hist_host = radix_classic_hist(&probe, (size_t)n, end_bit) != nullptr;
+    return 0;
+}
+
+extern "C" int gof_debug_scan_plan(int64_t n, uint32_t* tile_words_host, int32_t* launches_host)
+{
+    if (bad_count(n)) { set_error("scan plan: n = %lld must be in [0, 2^31)", (long long)n); return GOF_E_INVALID; }
+    const ScanPlan p = scan_plan((size_t)n);
+    if (tile_words_host) *tile_words_host = p.tile;
+    if (launches_host) *launches_host = n == 0 ? 0 : (p.direct ? 2 : 3);
+    return 0;
+}
+
+extern "C" int gof_debug_scan_u32(const uint32_t* in, const uint32_t* idx_or_null, uint32_t* out, int64_t n, int inclusive, void* ws, size_t ws_bytes,
+                                  uint32_t* total_out_dev, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (bad_count(n)) { set_error("debug scan: n = %lld must be in [0, 2^31)", (long long)n); return GOF_E_INVALID; }
+    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 3u)) { set_error("debug scan: the workspace is NULL or not 4-byte aligned"); return GOF_E_INVALID; }
+    if (n > 0 && (!in || !out)) { set_error("debug scan: in / out is NULL"); return GOF_E_INVALID; }
+    const size_t need = gof_debug_prim_ws_bytes(GOF_DEBUG_PRIM_SCAN, n, 0);
+    if (ws_bytes < need) { set_error("debug scan: the workspace has %zu bytes, gof_debug_prim_ws_bytes gives %zu", ws_bytes, need); return GOF_E_INVALID; }
+    const uint32_t* total = nullptr;
+    GOF_HIP_CHECK(device_scan_u32(in, idx_or_null, out, (size_t)n, inclusive != 0, static_cast<uint32_t*>(ws), &total, st));
+    if (total_out_dev) GOF_HIP_CHECK(hipMemcpyAsync(total_out_dev, total, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+extern "C" int gof_debug_radix_sort(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, int64_t n, int end_bit,
+                                    const uint32_t* n_dev_or_null, size_t zero_words_behind, int flags, void* ws, size_t ws_bytes,
+                                    int32_t* result_in_b_out, uint32_t* err_flag_out_dev, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (bad_count(n)) { set_error("debug sort: n = %lld must be in [0, 2^31)", (long long)n); return GOF_E_INVALID; }
+    if (end_bit < 1 || end_bit > 32) { set_error("debug sort: end_bit = %d must be in 1..32", end_bit); return GOF_E_INVALID; }
+    if (flags & ~(GOF_DEBUG_SORT_SCRATCH_ZEROED | GOF_DEBUG_SORT_FIRST_HIST_DONE)) { set_error("debug sort: unknown flags 0x%x", (unsigned)flags); return GOF_E_INVALID; }
+    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 3u)) { set_error("debug sort: the workspace is NULL or not 4-byte aligned"); return GOF_E_INVALID; }
+    if (!result_in_b_out) { set_error("debug sort: result_in_b_out is NULL"); return GOF_E_INVALID; }
+    if (n > 0 && (!keys_a || !vals_a || !keys_b || !vals_b)) { set_error("debug sort: a key / value buffer is NULL"); return GOF_E_INVALID; }
+    const size_t need = gof_debug_prim_ws_bytes(GOF_DEBUG_PRIM_SORT, n, zero_words_behind);
+    if (ws_bytes < need) { set_error("debug sort: the workspace has %zu bytes, gof_debug_prim_ws_bytes gives %zu", ws_bytes, need); return GOF_E_INVALID; }
+    uint32_t* tmp = static_cast<uint32_t*>(ws);
+    uint32_t *kr = nullptr, *vr = nullptr;
+    GOF_HIP_CHECK(radix_sort_pairs_u32_z(keys_a, vals_a, keys_b, vals_b, (size_t)n, end_bit, tmp, &kr, &vr, st, n_dev_or_null, zero_words_behind,
+                                         (flags & GOF_DEBUG_SORT_FIRST_HIST_DONE) != 0, (flags & GOF_DEBUG_SORT_SCRATCH_ZEROED) != 0));
+    if (n > 0 && (kr == keys_b) != (vr == vals_b)) { set_error("debug sort: keys and values ended in different buffer pairs"); return GOF_E_DEVICE; }
+    *result_in_b_out = (n > 0 && kr == keys_b) ? 1 : 0;      // (an empty sort runs no pass: its result is the a pair)
+    if (err_flag_out_dev) {
+        const uint32_t* err = radix_sort_error_flag(tmp, (size_t)n, end_bit);
+        if (err) GOF_HIP_CHECK(hipMemcpyAsync(err_flag_out_dev, err, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        else GOF_HIP_CHECK(hipMemsetAsync(err_flag_out_dev, 0, sizeof(uint32_t), st));
+    }
+    return 0;
+}
+
+extern "C" int gof_debug_sort_keys63(const unsigned long long* keys, int64_t n, void* ws, size_t ws_bytes, uint32_t* order_out, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (bad_count(n)) { set_error("debug sort63: n = %lld must be in [0, 2^31)", (long long)n); return GOF_E_INVALID; }
+    if (!ws) { set_error("debug sort63: the workspace is NULL"); return GOF_E_INVALID; }
+    if (n > 0 && (!keys || !order_out)) { set_error("debug sort63: keys / order_out is NULL"); return GOF_E_INVALID; }
+    const size_t need = gof_debug_prim_ws_bytes(GOF_DEBUG_PRIM_SORT63, n, 0);
+    if (ws_bytes < need) { set_error("debug sort63: the workspace has %zu bytes, gof_debug_prim_ws_bytes gives %zu", ws_bytes, need); return GOF_E_INVALID; }
+    Sort63Ws w;
+    debug_sort63_layout(ws_aligned(ws), (size_t)n, &w);
+    uint32_t* order = nullptr;
+    GOF_HIP_CHECK(sort63_keys_lo(keys, (size_t)n, w, st));
+    GOF_HIP_CHECK(sort_keys63(keys, (size_t)n, w, &order, st));
+    if (n > 0) GOF_HIP_CHECK(hipMemcpyAsync(order_out, order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    return 0;
+}

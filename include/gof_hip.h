@@ -424,6 +424,43 @@ int64_t gof_debug_fetch(const char* name, const GofRasterArgs* args, uint32_t nu
  * the faces chunk by chunk (32 Mi, tetmesh.py:55) is replaced by `chunk_size` for the calls that follow, so that the chunk arithmetic
  * can be tested at small sizes.  Returns the previous value; chunk_size <= 0 restores 32 Mi.  Process-wide, not thread-safe. */
 int64_t gof_debug_mtets_chunk(int64_t chunk_size);
+/* Test support, NOT part of the product's contract (may change with the tests): the library's shared device-wide scan and stable radix
+ * sort (csrc/radix.h), which every unit calls and no entry point exposes, on buffers the caller chooses.  Nothing is reimplemented: each
+ * entry checks its arguments (GOF_E_INVALID with gof_last_error() for n outside [0, 2^31), a NULL buffer with n > 0, end_bit outside
+ * 1..32, a workspace that is NULL, not 4-byte aligned or smaller than the query says), calls the primitive once and copies out what it
+ * left.  Asynchronous on `stream`.  tests/prim_cases.py, tests/test_primitives_{host,gpu}.py.
+ *   gof_debug_prim_ws_bytes:  bytes of `ws` for `kind` at n items; a sort's workspace is followed by its zero_words_behind words.
+ *   gof_debug_prim_constants: host only; items per sort block, passes of a sort on end_bit bits, the words at the start of a sort's
+ *                             workspace that a caller setting GOF_DEBUG_SORT_SCRATCH_ZEROED has cleared, and whether the sort runs as
+ *                             histogram / scan / scatter launches and takes a first histogram at the start of `ws`
+ *                             (GOF_DEBUG_SORT_FIRST_HIST_DONE: [256 digits][blocks that hold items] counts of key bits 0..7).  Each
+ *                             output pointer may be NULL.
+ *   gof_debug_scan_plan:      host only; the form a scan of n words runs in: words per workgroup, and its launches (2: every
+ *                             workgroup adds up its predecessors' sums itself; 3: a launch scans the sums; 0 for n == 0).
+ *   gof_debug_scan_u32:       out[i] = sum of in[j] (idx: in[idx[j]]) over j < i, or j <= i if inclusive, mod 2^32; out may be in;
+ *                             *total_out_dev (nullable) = the sum of all n.
+ *   gof_debug_radix_sort:     stable sort of the pairs in (keys_a, vals_a) by WHOLE 8-bit digits: key bits [0, 8 * ceil(end_bit / 8)).
+ *                             n_dev_or_null: the count lives on the device and n is the capacity.  *result_in_b_out (host) = 1 if the
+ *                             result lies in (keys_b, vals_b), 0 if in (keys_a, vals_a): the parity of the passes, 0 for n == 0.
+ *                             The zero_words_behind words at ws + gof_debug_prim_ws_bytes(SORT, n, 0) read zero afterwards.
+ *                             *err_flag_out_dev (nullable) = the sort's late-error word, 0 where it has none.
+ *   gof_debug_sort_keys63:    order_out[n] = the indices of the 63-bit keys (bit 63 clear) in ascending key order, equal keys in
+ *                             index order. */
+#define GOF_DEBUG_PRIM_SCAN   0
+#define GOF_DEBUG_PRIM_SORT   1
+#define GOF_DEBUG_PRIM_SORT63 2
+#define GOF_DEBUG_SORT_SCRATCH_ZEROED  1
+#define GOF_DEBUG_SORT_FIRST_HIST_DONE 2
+size_t gof_debug_prim_ws_bytes(int kind, int64_t n, size_t zero_words_behind);
+int gof_debug_prim_constants(int64_t n, int end_bit, uint32_t* block_items_host, int32_t* passes_host, size_t* zero_words_host,
+                             int32_t* classic_hist_host);
+int gof_debug_scan_plan(int64_t n, uint32_t* tile_words_host, int32_t* launches_host);
+int gof_debug_scan_u32(const uint32_t* in, const uint32_t* idx_or_null, uint32_t* out, int64_t n, int inclusive, void* ws, size_t ws_bytes,
+                       uint32_t* total_out_dev, void* stream);
+int gof_debug_radix_sort(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, int64_t n, int end_bit,
+                         const uint32_t* n_dev_or_null, size_t zero_words_behind, int flags, void* ws, size_t ws_bytes,
+                         int32_t* result_in_b_out, uint32_t* err_flag_out_dev, void* stream);
+int gof_debug_sort_keys63(const unsigned long long* keys, int64_t n, void* ws, size_t ws_bytes, uint32_t* order_out, void* stream);
 
 #ifdef __cplusplus
 }
